@@ -10,6 +10,13 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N>1
 launched via torch.distributed.run with one rank per GPU over RCCL.  W untimed
 warmup steps, then exactly K steps bracketed by barrier+synchronize on both
 sides, MAX elapsed over ranks, rank 0 prints ONE JSON line.
+
+A plain run does only that.  `--dump-outputs DIR` additionally writes what the
+last timed step returned (the loss terms) and a fixed seeded sample of the
+parameters it updated as DIR/<name>.npy (float32), so two builds can be
+compared output for output: model init, batches and dropout are all seeded.
+`--full` is where any secondary measurement belongs (extra precisions, sizes,
+baselines); there is none today, so it currently adds nothing to a plain run.
 """
 
 import argparse
@@ -44,6 +51,12 @@ def parse_args():
     p.add_argument("--model", default="gpt2",
                    choices=["gpt2", "bert-large", "llama7b", "llama1b", "vit-l16"],
                    help="flagship benchmark model family")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last step's outputs "
+                        "to DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (none exist yet; "
+                        "a plain run measures only the headline figure)")
     return p.parse_args()
 
 
@@ -138,6 +151,40 @@ def make_batch(args, micro, gen, device):
             "labels": toks[:, 1:].contiguous()}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_PER_PARAM = 4096
+
+
+def dump_outputs(out_dir, last_out, model):
+    """Write the last timed step's results as float32 .npy files: one
+    loss_<name>.npy per returned loss term and params_sample.npy, the same
+    seeded element sample of every updated parameter in named_parameters()
+    order (at most DUMP_PER_PARAM each, DUMP_BUDGET_BYTES in all)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    if isinstance(last_out, dict):
+        for k, v in last_out.items():
+            np.save(os.path.join(out_dir, f"loss_{k}.npy"),
+                    v.detach().float().cpu().numpy().astype(np.float32))
+    elif last_out is not None:
+        np.save(os.path.join(out_dir, "loss.npy"),
+                torch.as_tensor(last_out).detach().float().cpu().numpy()
+                .astype(np.float32))
+    params = [p for _, p in model.named_parameters()]
+    per = max(1, min(DUMP_PER_PARAM, DUMP_BUDGET_BYTES // 8 // max(len(params), 1)))
+    g = torch.Generator().manual_seed(97531)
+    parts = []
+    for p in params:
+        flat = p.detach().reshape(-1)
+        if flat.numel() > per:
+            idx = torch.randint(0, flat.numel(), (per,), generator=g)
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"),
+            torch.cat(parts).numpy().astype(np.float32))
+
+
 def main():
     args = parse_args()
     _enable_tuned_gemms()
@@ -228,13 +275,14 @@ def main():
         optimizer.grad_sync()
 
     step_i = 0
+    last_out = None  # what the latest step returned to its caller
 
     def one_step():
-        nonlocal step_i
+        nonlocal step_i, last_out
         if pipeline is not None:
             batches = [to_dev(pool[(step_i * args.acc + j) % len(pool)])
                        for j in range(max(args.acc, 1))]
-            pipeline.run_1f1b(batches)
+            last_out = pipeline.run_1f1b(batches)
         else:
             for j in range(args.acc):
                 data = to_dev(pool[(step_i * args.acc + j) % len(pool)])
@@ -243,6 +291,7 @@ def main():
                 losses = model(**data)
                 total = sum(v for v in losses.values()) / args.acc
                 total.backward()
+            last_out = {k: v.detach() for k, v in losses.items()}
         sync_dp_grads()
         optimizer.step()
         optimizer.zero_grad()
@@ -279,6 +328,9 @@ def main():
         par += f"_tp{args.tp}"
     if args.pp > 1:
         par += f"_pp{args.pp}"
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out, model)
 
     if rank == 0:
         print(
