@@ -94,7 +94,7 @@ void flash_fwd_bf16(const void*, const void*, const void*, void*, float*,
                     const int*, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int, int, int, int, int, float, float, uint64_t, int, int,
-                    hipStream_t);
+                    const float*, hipStream_t);
 void flash_bwd_bf16(const void*, const void*, const void*, const void*, const void*,
                     const float*, float*, const int*, void*, void*, void*, int64_t,
                     int64_t,
@@ -102,7 +102,7 @@ void flash_bwd_bf16(const void*, const void*, const void*, const void*, const vo
                     int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int64_t, int, int, int, int, int, float, float, uint64_t, int,
-                    int, hipStream_t);
+                    int, const float*, hipStream_t);
 void attn_dropout_apply_bf16(void*, int64_t, int64_t, int64_t, float, uint64_t,
                              hipStream_t);
 void attn_dropout_apply_f32(void*, int64_t, int64_t, int64_t, float, uint64_t,
@@ -120,13 +120,13 @@ void gemm_dw_bf16(const void*, const void*, float*, void*, int, int64_t, int64_t
 void flash_decode_bf16(const void*, const void*, const void*, void*, const int*,
                        int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                        int64_t, int64_t, int64_t, int64_t, int, int, int, int,
-                       float, int, hipStream_t);
+                       float, int, const float*, hipStream_t);
 int flash_decode_num_splits(int, int, int);
 void flash_decode_split_bf16(const void*, const void*, const void*, void*,
                              float*, float*, float*, const int*, int64_t,
                              int64_t, int64_t, int64_t, int64_t, int64_t,
                              int64_t, int64_t, int64_t, int64_t, int, int, int,
-                             int, int, float, int, hipStream_t);
+                             int, int, float, int, const float*, hipStream_t);
 void rope_fwd_bf16(const void*, void*, const float*, const float*, int64_t, int64_t,
                    int64_t, int64_t, int64_t, int64_t, int, int, int, int, int,
                    hipStream_t);
@@ -414,11 +414,24 @@ torch::Tensor gemm_dw(torch::Tensor dy, torch::Tensor x, int64_t splits) {
 }
 
 
+// optional ALiBi slopes: one fp32 per QUERY head of the call
+static const float* alibi_slopes_ptr(const c10::optional<torch::Tensor>& slopes,
+                                     const torch::Tensor& q, int64_t H) {
+  if (!slopes.has_value()) return nullptr;
+  TORCH_CHECK(slopes->scalar_type() == torch::kFloat32 && slopes->is_cuda() &&
+                  slopes->get_device() == q.get_device() &&
+                  slopes->is_contiguous() && slopes->numel() == H,
+              "alibi_slopes must be a contiguous fp32 tensor of size H (query "
+              "heads) on q's device");
+  return slopes->data_ptr<float>();
+}
+
 // ---------------------------------------------------------------------------
 // fused single-query decode attention (K16 serving path)
 // ---------------------------------------------------------------------------
 torch::Tensor flash_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                           double scale, c10::optional<torch::Tensor> kv_len) {
+                           double scale, c10::optional<torch::Tensor> kv_len,
+                           c10::optional<torch::Tensor> alibi_slopes) {
   // q: [B, H, 1, D]; k/v: [B, Hkv, Skv, D] (the decode KV-cache layout)
   TORCH_CHECK(q.dim() == 4 && q.size(2) == 1, "flash_decode: q must be [B,H,1,D]");
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "flash_decode is bf16-only");
@@ -433,6 +446,7 @@ torch::Tensor flash_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                 kv_len->numel() == B);
     kvl = kv_len->data_ptr<int>();
   }
+  const float* slopes = alibi_slopes_ptr(alibi_slopes, q, H);
   auto o = torch::empty({B, H, 1, D}, q.options());
   const int S = flash_decode_num_splits(B, H, Skv);
   if (S > 1) {
@@ -448,13 +462,13 @@ torch::Tensor flash_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
         pm.data_ptr<float>(), pl.data_ptr<float>(), pa.data_ptr<float>(), kvl,
         q.stride(0), q.stride(1), k.stride(0), k.stride(2), k.stride(1),
         v.stride(0), v.stride(2), v.stride(1), o.stride(0), o.stride(1), B, H,
-        S, Skv, D, (float)scale, H / Hkv, cur_stream());
+        S, Skv, D, (float)scale, H / Hkv, slopes, cur_stream());
   } else {
     flash_decode_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                       kvl, q.stride(0), q.stride(1), k.stride(0), k.stride(2),
                       k.stride(1), v.stride(0), v.stride(2), v.stride(1),
                       o.stride(0), o.stride(1), B, H, Skv, D, (float)scale,
-                      H / Hkv, cur_stream());
+                      H / Hkv, slopes, cur_stream());
   }
   check_launch("flash_decode");
   return o;
@@ -513,7 +527,8 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
                                                    torch::Tensor v, double scale,
                                                    double p_drop, int64_t seed,
                                                    bool causal,
-                                                   c10::optional<torch::Tensor> kv_len) {
+                                                   c10::optional<torch::Tensor> kv_len,
+                                                   c10::optional<torch::Tensor> alibi_slopes) {
   const int* kvl = nullptr;
   if (kv_len.has_value()) {
     TORCH_CHECK(kv_len->scalar_type() == torch::kInt32 && kv_len->is_cuda() &&
@@ -534,6 +549,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
   TORCH_CHECK(Hkv > 0 && H % Hkv == 0 && (int)v.size(2) == Hkv,
               "GQA head counts: H divisible by Hkv, v matches k");
   const int kv_group = H / Hkv;
+  const float* slopes = alibi_slopes_ptr(alibi_slopes, q, H);
   auto o = torch::empty({B, Sq, H, D}, q.options());
   auto lse = torch::empty({B, H, Sq}, q.options().dtype(torch::kFloat32));
   flash_fwd_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
@@ -541,7 +557,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
                  k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1),
                  v.stride(2), o.stride(0), o.stride(1), o.stride(2), B, H, Sq, Sk, D,
                  (float)scale, (float)p_drop, (uint64_t)seed, causal ? 1 : 0,
-                 kv_group, cur_stream());
+                 kv_group, slopes, cur_stream());
   check_launch("flash_fwd");
   return {o, lse};
 }
@@ -550,7 +566,8 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> flash_bwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o,
     torch::Tensor dout, torch::Tensor lse, double scale, double p_drop, int64_t seed,
     bool causal, c10::optional<torch::Tensor> dqkv,
-    c10::optional<torch::Tensor> kv_len) {
+    c10::optional<torch::Tensor> kv_len,
+    c10::optional<torch::Tensor> alibi_slopes) {
   const int* kvl = nullptr;
   if (kv_len.has_value()) {
     TORCH_CHECK(kv_len->scalar_type() == torch::kInt32 && kv_len->is_cuda() &&
@@ -562,6 +579,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> flash_bwd(
             D = (int)q.size(3);
   const int Sk = (int)k.size(1), Hkv = (int)k.size(2);
   const int kv_group = H / Hkv;
+  const float* slopes = alibi_slopes_ptr(alibi_slopes, q, H);
   TORCH_CHECK(dout.is_contiguous() && o.is_contiguous());
   torch::Tensor dq, dk, dv;
   if (dqkv.has_value()) {
@@ -585,7 +603,8 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> flash_bwd(
       o.stride(2), dout.stride(0), dout.stride(1), dout.stride(2), dq.stride(0),
       dq.stride(1), dq.stride(2), dk.stride(0), dk.stride(1), dk.stride(2),
       dv.stride(0), dv.stride(1), dv.stride(2), B, H, Sq, Sk, D, (float)scale,
-      (float)p_drop, (uint64_t)seed, causal ? 1 : 0, kv_group, cur_stream());
+      (float)p_drop, (uint64_t)seed, causal ? 1 : 0, kv_group, slopes,
+      cur_stream());
   check_launch("flash_bwd");
   return {dq, dk, dv};
 }
@@ -752,11 +771,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lt_dgelu_bgrad", &lt_dgelu_bgrad);
   m.def("lt_epilogues_available", &lt_epilogues_available);
   m.def("gemm_dw", &gemm_dw);
-  m.def("flash_decode", &flash_decode);
+  m.def("flash_decode", &flash_decode, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("scale"), py::arg("kv_len"),
+        py::arg("alibi_slopes") = py::none());
   m.def("embedding_fwd", &embedding_fwd);
   m.def("embedding_bwd", &embedding_bwd);
-  m.def("flash_fwd", &flash_fwd);
-  m.def("flash_bwd", &flash_bwd);
+  m.def("flash_fwd", &flash_fwd, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("scale"), py::arg("p_drop"), py::arg("seed"), py::arg("causal"),
+        py::arg("kv_len"), py::arg("alibi_slopes") = py::none());
+  m.def("flash_bwd", &flash_bwd, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("o"), py::arg("dout"), py::arg("lse"), py::arg("scale"),
+        py::arg("p_drop"), py::arg("seed"), py::arg("causal"), py::arg("dqkv"),
+        py::arg("kv_len"), py::arg("alibi_slopes") = py::none());
   m.def("attn_dropout_apply", &attn_dropout_apply);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);

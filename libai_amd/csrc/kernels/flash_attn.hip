@@ -186,14 +186,20 @@ __device__ __forceinline__ float drop_keep(uint64_t seed, uint64_t bh, int64_t S
 // ===========================================================================
 // forward
 // ===========================================================================
-template <int D>
+// ALIBI: compile-time variant that adds slope[h] * (kv - q) to every
+// pre-softmax score (fp32, one slope per QUERY head).  The (kv - q) form is
+// row-shift-equivalent to BLOOM's slope * kv under softmax, is bounded by the
+// sequence length and is <= 0 under the causal mask.  The ALIBI=false
+// instantiations never touch the pointer.
+template <int D, bool ALIBI>
 __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, bf16_t* __restrict__ o, float* __restrict__ lse,
     const int* __restrict__ kv_len, int64_t q_sb, int64_t q_ss, int64_t q_sh,
     int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss,
     int64_t v_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh, int H, int Sq, int Sk,
-    float scale, float p_drop, uint64_t seed, int causal, int kv_group) {
+    float scale, float p_drop, uint64_t seed, int causal, int kv_group,
+    const float* __restrict__ alibi_slopes) {
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
 
@@ -247,6 +253,9 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
   const int n_rounds = CDIV(kv_end, 2 * KVB);
   const float ks = (p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
   const int qg = q_base + l31;
+  // scores live in the exp2 domain, so the slope is pre-multiplied by log2e
+  float slope2 = 0.f;
+  if constexpr (ALIBI) slope2 = alibi_slopes[h] * 1.4426950408889634f;
 
   for (int round = 0; round < n_rounds; ++round) {
     const int kvR = round * 2 * KVB;
@@ -275,11 +284,20 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     // scores are already in the exp2 domain (Q pre-scale); m/l run in it too
     float sv[2][16];
     float pmax = -3.0e38f;
+    // kv - q of this lane's first score; the per-register offsets below are
+    // compile-time constants (exact in fp32)
+    float rel0 = 0.f;
+    if constexpr (ALIBI) rel0 = (float)(kv0 + 4 * hi - qg);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       int kva = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
       int kvb = kva + 32;
       float a = s0[r], bb = s1[r];
+      if constexpr (ALIBI) {  // before the masks: masked entries keep the sentinel
+        const float off = (float)((r & 3) + 8 * (r >> 2));
+        a = fmaf(slope2, rel0 + off, a);
+        bb = fmaf(slope2, rel0 + (off + 32.f), bb);
+      }
       if (kva >= sk_eff || (causal && kva > qg)) a = -3.0e38f;
       if (kvb >= sk_eff || (causal && kvb > qg)) bb = -3.0e38f;
       sv[0][r] = a;
@@ -405,8 +423,14 @@ __global__ void rowdot_kernel(const bf16_t* __restrict__ dout,
 #define BWD_KV_NBUF 1
 #define BWD_KV_OCC 3
 #endif
-template <int D>
-__global__ __launch_bounds__(256, D == 64 ? BWD_KV_OCC : 2) void flash_bwd_kv_kernel(
+// The D=64 ALiBi instantiation targets 2 waves/SIMD: at 3 (168 VGPRs) the
+// extra term pushes the staging-address spills from 64 to 72 B/lane, at 2 it
+// takes 202 VGPRs with no scratch and measured faster on MI355X (b4 s1024 h16
+// fwd+bwd 293 us vs 333 us, profiles/alibi_flash.md).  The non-ALiBi
+// instantiation keeps its target.
+template <int D, bool ALIBI>
+__global__ __launch_bounds__(256, D == 64 ? (ALIBI ? 2 : BWD_KV_OCC)
+                                          : 2) void flash_bwd_kv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ drow,
@@ -416,7 +440,7 @@ __global__ __launch_bounds__(256, D == 64 ? BWD_KV_OCC : 2) void flash_bwd_kv_ke
     int64_t v_ss, int64_t v_sh, int64_t do_sb, int64_t do_ss, int64_t do_sh,
     int64_t dk_sb, int64_t dk_ss, int64_t dk_sh, int64_t dv_sb, int64_t dv_ss,
     int64_t dv_sh, int H, int Sq, int Sk, float scale, float p_drop, uint64_t seed,
-    int causal, int kv_group) {
+    int causal, int kv_group, const float* __restrict__ alibi_slopes) {
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
   // D=64: 64-row staging tiles + persistent K/V fragments.  D=128: 32-row
@@ -483,6 +507,9 @@ __global__ __launch_bounds__(256, D == 64 ? BWD_KV_OCC : 2) void flash_bwd_kv_ke
   const int bh = b * H + h;  // q-head index: lse/drow rows + dropout key
   const bf16_t* qp = q + b * q_sb + h * q_sh;
   const bf16_t* dop = dout + b * do_sb + h * do_sh;
+  // ALiBi slope of THIS query head (the grid spans kv heads)
+  float slope = 0.f;
+  if constexpr (ALIBI) slope = alibi_slopes[h];
 
   auto stage_all = [&](int buf, int qt) {
     const int q0 = qt * QTILE;
@@ -559,7 +586,11 @@ __global__ __launch_bounds__(256, D == 64 ? BWD_KV_OCC : 2) void flash_bwd_kv_ke
             const bool valid =
                 qrow < Sq && kvg < sk_eff && (!causal || qrow >= kvg);
             float p = 0.f;
-            if (valid) p = __expf(s[r] * scale - lse_lds[buf][qrow - q0]);
+            float sc = s[r] * scale;
+            // (kv - q) is recomputed per element: nothing extra stays live
+            // across the subtile on this kernel's register budget
+            if constexpr (ALIBI) sc = fmaf(slope, (float)(kvg - qrow), sc);
+            if (valid) p = __expf(sc - lse_lds[buf][qrow - q0]);
             float keep = valid ? 1.f : 0.f;
             if (p_drop > 0.f && valid)
               keep = (((hqj[j] >> byte_sh) & 0xFFu) >= thr8) ? ks : 0.f;
@@ -637,7 +668,7 @@ __global__ __launch_bounds__(256, D == 64 ? BWD_KV_OCC : 2) void flash_bwd_kv_ke
 // ===========================================================================
 // backward over q tiles: dQ   (block = 128 q rows, wave owns 32; fwd-like)
 // ===========================================================================
-template <int D>
+template <int D, bool ALIBI>
 __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
@@ -647,7 +678,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
     int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss, int64_t v_sh,
     int64_t do_sb, int64_t do_ss, int64_t do_sh, int64_t dq_sb, int64_t dq_ss,
     int64_t dq_sh, int H, int Sq, int Sk, float scale, float p_drop, uint64_t seed,
-    int causal, int kv_group) {
+    int causal, int kv_group, const float* __restrict__ alibi_slopes) {
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
   constexpr int KVTILE = (D == 64) ? 2 * QB : QB;
@@ -696,6 +727,8 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
   };
   const float lse_lane = lse[(int64_t)bh * Sq + min(qg, Sq - 1)];
   const float drow_lane = drow[(int64_t)bh * Sq + min(qg, Sq - 1)];
+  float slope = 0.f;
+  if constexpr (ALIBI) slope = alibi_slopes[h];
 
   f32x16_t dq_acc[DT];
 #pragma unroll
@@ -736,6 +769,9 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
 
       float ds[16];
       const uint32_t thr8 = drop_threshold_u8(p_drop);
+      // kv - q of this lane's first score (ALiBi)
+      float rel0 = 0.f;
+      if constexpr (ALIBI) rel0 = (float)(kv0s + 4 * hi - qg);
 #pragma unroll
       for (int r4 = 0; r4 < 4; ++r4) {
         const int kvb = kv0s + 8 * r4 + 4 * hi;  // 4-aligned kv run
@@ -747,7 +783,9 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
           const int r = r4 * 4 + j;
           const int kv = kvb + j;
           const bool valid = kv < sk_eff && qg < Sq && (!causal || kv <= qg);
-          float p = valid ? __expf(st[r] * scale - lse_lane) : 0.f;
+          float sc = st[r] * scale;
+          if constexpr (ALIBI) sc = fmaf(slope, rel0 + (float)(8 * r4 + j), sc);
+          float p = valid ? __expf(sc - lse_lane) : 0.f;
           float keep = (p_drop > 0.f && valid) ? drop_keep_byte(h, j, thr8, ks)
                                                : (valid ? 1.f : 0.f);
           ds[r] = valid ? scale * p * (dpdt[r] * keep - drow_lane) : 0.f;
@@ -813,19 +851,27 @@ extern "C" void flash_fwd_bf16(const void* q, const void* k, const void* v, void
                                int64_t v_ss, int64_t v_sh, int64_t o_sb, int64_t o_ss,
                                int64_t o_sh, int B, int H, int Sq, int Sk, int D,
                                float scale, float p_drop, uint64_t seed, int causal,
-                               int kv_group, hipStream_t stream) {
+                               int kv_group, const float* alibi_slopes,
+                               hipStream_t stream) {
   dim3 grid(CDIV(Sq, QBLK), B * H);
   dim3 block(256);
-  if (D == 64)
-    flash_fwd_kernel<64><<<grid, block, 0, stream>>>(
-        (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse,
-        kv_len, q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, o_sb, o_ss,
-        o_sh, H, Sq, Sk, scale, p_drop, seed, causal, kv_group);
-  else if (D == 128)
-    flash_fwd_kernel<128><<<grid, block, 0, stream>>>(
-        (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse,
-        kv_len, q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, o_sb, o_ss,
-        o_sh, H, Sq, Sk, scale, p_drop, seed, causal, kv_group);
+#define FWD_ARGS                                                                     \
+  (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, kv_len,     \
+      q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, o_sb, o_ss, o_sh, H, Sq, \
+      Sk, scale, p_drop, seed, causal, kv_group, alibi_slopes
+  const bool alibi = alibi_slopes != nullptr;
+  if (D == 64) {
+    if (alibi)
+      flash_fwd_kernel<64, true><<<grid, block, 0, stream>>>(FWD_ARGS);
+    else
+      flash_fwd_kernel<64, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+  } else if (D == 128) {
+    if (alibi)
+      flash_fwd_kernel<128, true><<<grid, block, 0, stream>>>(FWD_ARGS);
+    else
+      flash_fwd_kernel<128, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+  }
+#undef FWD_ARGS
 }
 
 extern "C" void flash_bwd_bf16(
@@ -838,7 +884,7 @@ extern "C" void flash_bwd_bf16(
     int64_t dq_ss, int64_t dq_sh, int64_t dk_sb, int64_t dk_ss, int64_t dk_sh,
     int64_t dv_sb, int64_t dv_ss, int64_t dv_sh, int B, int H, int Sq, int Sk, int D,
     float scale, float p_drop, uint64_t seed, int causal, int kv_group,
-    hipStream_t stream) {
+    const float* alibi_slopes, hipStream_t stream) {
   // Drow = rowsum(dO * O)  (dO and O share layout; use dO's strides for both:
   // the wrapper guarantees o was allocated with the same layout)
   {
@@ -859,25 +905,29 @@ extern "C" void flash_bwd_bf16(
   (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse,    \
       drow_ws, kv_len, (bf16_t*)dk, (bf16_t*)dv, q_sb, q_ss, q_sh, k_sb, k_ss,       \
       k_sh, v_sb, v_ss, v_sh, do_sb, do_ss, do_sh, dk_sb, dk_ss, dk_sh, dv_sb,       \
-      dv_ss, dv_sh, H, Sq, Sk, scale, p_drop, seed, causal, kv_group
+      dv_ss, dv_sh, H, Sq, Sk, scale, p_drop, seed, causal, kv_group, alibi_slopes
 #define BWD_ARGS_Q                                                                   \
   (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse,    \
       drow_ws, kv_len, (bf16_t*)dq, q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss,  \
       v_sh, do_sb, do_ss, do_sh, dq_sb, dq_ss, dq_sh, H, Sq, Sk, scale, p_drop,      \
-      seed, causal, kv_group
+      seed, causal, kv_group, alibi_slopes
   dim3 block(256);
   const int Hkv = H / kv_group;  // bwd_kv grid spans the KV heads
+  const dim3 grid_kv(CDIV(Sk, QBLK), B * Hkv), grid_q(CDIV(Sq, QBLK), B * H);
+#define BWD_LAUNCH(DD, AL)                                                           \
+  do {                                                                               \
+    flash_bwd_kv_kernel<DD, AL><<<grid_kv, block, 0, stream>>>(BWD_ARGS_KV);         \
+    flash_bwd_q_kernel<DD, AL><<<grid_q, block, 0, stream>>>(BWD_ARGS_Q);            \
+  } while (0)
+  const bool alibi = alibi_slopes != nullptr;
   if (D == 64) {
-    flash_bwd_kv_kernel<64>
-        <<<dim3(CDIV(Sk, QBLK), B * Hkv), block, 0, stream>>>(BWD_ARGS_KV);
-    flash_bwd_q_kernel<64>
-        <<<dim3(CDIV(Sq, QBLK), B * H), block, 0, stream>>>(BWD_ARGS_Q);
+    if (alibi) BWD_LAUNCH(64, true);
+    else BWD_LAUNCH(64, false);
   } else if (D == 128) {
-    flash_bwd_kv_kernel<128>
-        <<<dim3(CDIV(Sk, QBLK), B * Hkv), block, 0, stream>>>(BWD_ARGS_KV);
-    flash_bwd_q_kernel<128>
-        <<<dim3(CDIV(Sq, QBLK), B * H), block, 0, stream>>>(BWD_ARGS_Q);
+    if (alibi) BWD_LAUNCH(128, true);
+    else BWD_LAUNCH(128, false);
   }
+#undef BWD_LAUNCH
 }
 
 #define ATTN_DROP_LAUNCHER(SUFF, ETYPE)                                            \

@@ -19,13 +19,17 @@ namespace {
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
-template <int D>
+// ALIBI: compile-time variant adding slope[h] * (key - qpos) to each score,
+// qpos = kv_len[b] - 1 (the new token is the last cached key).  Same (kv - q)
+// form as the training kernels; one fp32 slope per QUERY head.
+template <int D, bool ALIBI>
 __global__ __launch_bounds__(256, 4) void flash_decode_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, bf16_t* __restrict__ o,
     const int* __restrict__ kv_len, int64_t q_sb, int64_t q_sh, int64_t k_sb,
     int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss, int64_t v_sh,
-    int64_t o_sb, int64_t o_sh, int H, int Skv, float scale, int kv_group) {
+    int64_t o_sb, int64_t o_sh, int H, int Skv, float scale, int kv_group,
+    const float* __restrict__ alibi_slopes) {
   constexpr int DPL = D / 64;  // dims per lane
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -35,6 +39,8 @@ __global__ __launch_bounds__(256, 4) void flash_decode_kernel(
   const int b = bh / H, h = bh % H;
   const int hk = h / kv_group;
   const int skv = (kv_len != nullptr) ? kv_len[b] : Skv;
+  float slope = 0.f;
+  if constexpr (ALIBI) slope = alibi_slopes[h];
 
   const bf16_t* qp = q + b * q_sb + h * q_sh;
   const bf16_t* kp = k + b * k_sb + hk * k_sh;
@@ -68,6 +74,7 @@ __global__ __launch_bounds__(256, 4) void flash_decode_kernel(
         for (int j = 0; j < 8; ++j) dot += bf2f(qreg[c][j]) * bf2f(kv8[j]);
       }
       s = dot * scale;
+      if constexpr (ALIBI) s = fmaf(slope, (float)(key - (skv - 1)), s);
     }
     const float cmax = wave_reduce_max(s);
     const float m_new = fmaxf(m_run, cmax);
@@ -132,14 +139,18 @@ __global__ __launch_bounds__(256, 4) void flash_decode_kernel(
 // ---------------------------------------------------------------------------
 constexpr int SPLIT_KEYS = 512;
 
-template <int D>
+// ALIBI: every split uses the SAME per-batch query position kv_len[b] - 1,
+// so the cross-split merge stays valid and the outputs stay bitwise
+// independent of the cache capacity.
+template <int D, bool ALIBI>
 __global__ __launch_bounds__(256, 4) void flash_decode_split_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, float* __restrict__ part_m,
     float* __restrict__ part_l, float* __restrict__ part_acc,
     const int* __restrict__ kv_len, int64_t q_sb, int64_t q_sh, int64_t k_sb,
     int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss, int64_t v_sh,
-    int H, int S, int Skv, float scale, int kv_group) {
+    int H, int S, int Skv, float scale, int kv_group,
+    const float* __restrict__ alibi_slopes) {
   constexpr int DPL = D / 64;
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -170,6 +181,8 @@ __global__ __launch_bounds__(256, 4) void flash_decode_split_kernel(
   const bf16_t* qp = q + b * q_sb + h * q_sh;
   const bf16_t* kp = k + b * k_sb + hk * k_sh;
   const bf16_t* vp = v + b * v_sb + hk * v_sh;
+  float slope = 0.f;
+  if constexpr (ALIBI) slope = alibi_slopes[h];
 
   u16x8 qreg[D / 8];
 #pragma unroll
@@ -197,6 +210,7 @@ __global__ __launch_bounds__(256, 4) void flash_decode_split_kernel(
         for (int j = 0; j < 8; ++j) dot += bf2f(qreg[c][j]) * bf2f(kv8[j]);
       }
       s = dot * scale;
+      if constexpr (ALIBI) s = fmaf(slope, (float)(key - (skv - 1)), s);
     }
     const float cmax = wave_reduce_max(s);
     const float m_new = fmaxf(m_run, cmax);
@@ -297,18 +311,26 @@ extern "C" void flash_decode_bf16(const void* q, const void* k, const void* v,
                                   int64_t k_sh, int64_t v_sb, int64_t v_ss,
                                   int64_t v_sh, int64_t o_sb, int64_t o_sh, int B,
                                   int H, int Skv, int D, float scale,
-                                  int kv_group, hipStream_t stream) {
+                                  int kv_group, const float* alibi_slopes,
+                                  hipStream_t stream) {
   dim3 grid(B * H);
-  if (D == 64)
-    flash_decode_kernel<64><<<grid, dim3(256), 0, stream>>>(
-        (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, kv_len,
-        q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, o_sb, o_sh, H, Skv,
-        scale, kv_group);
-  else if (D == 128)
-    flash_decode_kernel<128><<<grid, dim3(256), 0, stream>>>(
-        (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, kv_len,
-        q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, o_sb, o_sh, H, Skv,
-        scale, kv_group);
+#define DECODE_ARGS                                                            \
+  (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, kv_len,    \
+      q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, o_sb, o_sh, H, Skv,      \
+      scale, kv_group, alibi_slopes
+  const bool alibi = alibi_slopes != nullptr;
+  if (D == 64) {
+    if (alibi)
+      flash_decode_kernel<64, true><<<grid, dim3(256), 0, stream>>>(DECODE_ARGS);
+    else
+      flash_decode_kernel<64, false><<<grid, dim3(256), 0, stream>>>(DECODE_ARGS);
+  } else if (D == 128) {
+    if (alibi)
+      flash_decode_kernel<128, true><<<grid, dim3(256), 0, stream>>>(DECODE_ARGS);
+    else
+      flash_decode_kernel<128, false><<<grid, dim3(256), 0, stream>>>(DECODE_ARGS);
+  }
+#undef DECODE_ARGS
 }
 
 extern "C" void flash_decode_split_bf16(
@@ -316,21 +338,28 @@ extern "C" void flash_decode_split_bf16(
     float* part_l, float* part_acc, const int* kv_len, int64_t q_sb,
     int64_t q_sh, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sb,
     int64_t v_ss, int64_t v_sh, int64_t o_sb, int64_t o_sh, int B, int H,
-    int S, int Skv, int D, float scale, int kv_group, hipStream_t stream) {
+    int S, int Skv, int D, float scale, int kv_group, const float* alibi_slopes,
+    hipStream_t stream) {
   dim3 grid(B * H * S), mgrid(B * H);
+#define SPLIT_ARGS                                                             \
+  (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, part_m, part_l,        \
+      part_acc, kv_len, q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, H, S,  \
+      Skv, scale, kv_group, alibi_slopes
+  const bool alibi = alibi_slopes != nullptr;
   if (D == 64) {
-    flash_decode_split_kernel<64><<<grid, dim3(256), 0, stream>>>(
-        (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, part_m, part_l,
-        part_acc, kv_len, q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, H, S,
-        Skv, scale, kv_group);
+    if (alibi)
+      flash_decode_split_kernel<64, true><<<grid, dim3(256), 0, stream>>>(SPLIT_ARGS);
+    else
+      flash_decode_split_kernel<64, false><<<grid, dim3(256), 0, stream>>>(SPLIT_ARGS);
     flash_decode_merge_kernel<64><<<mgrid, dim3(64), 0, stream>>>(
         part_m, part_l, part_acc, (bf16_t*)o, H, S, o_sb, o_sh);
   } else if (D == 128) {
-    flash_decode_split_kernel<128><<<grid, dim3(256), 0, stream>>>(
-        (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, part_m, part_l,
-        part_acc, kv_len, q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, H, S,
-        Skv, scale, kv_group);
+    if (alibi)
+      flash_decode_split_kernel<128, true><<<grid, dim3(256), 0, stream>>>(SPLIT_ARGS);
+    else
+      flash_decode_split_kernel<128, false><<<grid, dim3(256), 0, stream>>>(SPLIT_ARGS);
     flash_decode_merge_kernel<128><<<mgrid, dim3(64), 0, stream>>>(
         part_m, part_l, part_acc, (bf16_t*)o, H, S, o_sb, o_sh);
   }
+#undef SPLIT_ARGS
 }

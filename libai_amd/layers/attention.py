@@ -157,13 +157,22 @@ class MultiheadAttention(nn.Module):
             # returns RAW (out, bias): the layer fuses bias+residual+norm
             return self.dense(context)
 
+        # an ALiBi bias from build_alibi_bias carries its fp32 slopes: the
+        # fused kernels add slope * (kv - q) in-register and never read the
+        # tensor.  Any other bias (T5, user-supplied) has no slopes and takes
+        # the materialized path below.
+        from ..ops.attention import bias_alibi_slopes
+
+        slopes = bias_alibi_slopes(position_bias)
+        bias_fusable = position_bias is None or slopes is not None
+
         # fused flash path: consumes the qkv buffer with ZERO copies (strided
         # [b, s, nh, hs] views), O lands directly in [b, s, h] layout.
         if (
             not self.is_cross_attention
             and past_key_value is None
             and not use_cache
-            and position_bias is None
+            and bias_fusable
         ):
             from ..ops.attention import (
                 flash_attention_available,
@@ -187,6 +196,7 @@ class MultiheadAttention(nn.Module):
                     causal=self.attn_mask_type == AttnMaskType.causal,
                     training=self.training,
                     kv_len=mask_kv_len(attention_mask),
+                    alibi_slopes=slopes,
                 )
                 context = o.reshape(b, s, self.num_heads_local * self.head_size)
                 out, bias = self.dense(context)
@@ -213,7 +223,7 @@ class MultiheadAttention(nn.Module):
         if (
             past_key_value is not None
             and attention_mask is None
-            and position_bias is None
+            and bias_fusable
             and not self.is_cross_attention
         ):
             from ..ops.attention import (
@@ -223,7 +233,10 @@ class MultiheadAttention(nn.Module):
 
             if decode_attention_available(q, self.head_size):
                 # fused single-token decode (K16): no [b, nh, 1, skv] scores
-                ctx = flash_decode_attn(q.contiguous(), k, v, scale_d)
+                # (ALiBi: the new token is the last key, so key index ==
+                # absolute position and the kernel's qpos = skv - 1)
+                ctx = flash_decode_attn(q.contiguous(), k, v, scale_d,
+                                        alibi_slopes=slopes)
                 b, nh, _, hs = ctx.shape
                 context = ctx.permute(0, 2, 1, 3).reshape(b, 1, nh * hs)
                 out, bias = self.dense(context)

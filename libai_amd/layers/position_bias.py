@@ -13,7 +13,8 @@ from torch import nn
 
 from ..utils import distributed as du
 
-__all__ = ["T5RelativePositionBias", "build_alibi_bias", "alibi_slopes"]
+__all__ = ["T5RelativePositionBias", "build_alibi_bias", "alibi_slopes",
+           "local_alibi_slopes"]
 
 
 class T5RelativePositionBias(nn.Module):
@@ -84,14 +85,27 @@ def alibi_slopes(num_heads):
     return torch.tensor(slopes)
 
 
-def build_alibi_bias(num_heads, seq_len, device=None, dtype=torch.float32):
-    """[nh_local, 1, seq] ALiBi bias (this TP rank's head slice).
-
-    slope_h * j is row-shift-equivalent to slope_h * (j - i) under softmax,
-    so the per-query term is dropped (BLOOM's own formulation)."""
+def local_alibi_slopes(num_heads, device=None):
+    """fp32 [nh_local] slopes of this TP rank's head slice (contiguous)."""
     dutil = du.get_dist_util()
     tp, tpr = dutil.tensor_parallel_size, dutil.tensor_parallel_rank
     slopes = alibi_slopes(num_heads).to(device=device, dtype=torch.float32)
     local = slopes.chunk(tp)[tpr] if tp > 1 else slopes
+    return local.contiguous()
+
+
+def build_alibi_bias(num_heads, seq_len, device=None, dtype=torch.float32):
+    """[nh_local, 1, seq] ALiBi bias (this TP rank's head slice).
+
+    slope_h * j is row-shift-equivalent to slope_h * (j - i) under softmax,
+    so the per-query term is dropped (BLOOM's own formulation).
+
+    The fp32 slopes ride along as ``bias._alibi_slopes`` (the convention
+    ``extended_attn_mask`` uses for ``_kv_len``): attention layers that see
+    the attribute know the bias is exactly ALiBi and hand the slopes to the
+    fused kernels instead of adding the tensor to materialized scores."""
+    local = local_alibi_slopes(num_heads, device)
     pos = torch.arange(seq_len, device=device, dtype=torch.float32)
-    return (local[:, None, None] * pos[None, None, :]).to(dtype)
+    bias = (local[:, None, None] * pos[None, None, :]).to(dtype)
+    bias._alibi_slopes = local
+    return bias
