@@ -4,6 +4,7 @@
 // csrc/kernels/*.hip, compiled by hipcc for gfx950 and linked in.  The split
 // keeps torch headers out of hipcc (seconds-per-kernel compiles) and keeps the
 // device code pure HIP.
+#include <algorithm>
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime_api.h>
@@ -94,7 +95,7 @@ void flash_fwd_bf16(const void*, const void*, const void*, void*, float*,
                     const int*, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int, int, int, int, int, float, float, uint64_t, int, int,
-                    const float*, hipStream_t);
+                    const float*, int, hipStream_t);
 void flash_bwd_bf16(const void*, const void*, const void*, const void*, const void*,
                     const float*, float*, const int*, void*, void*, void*, int64_t,
                     int64_t,
@@ -102,7 +103,7 @@ void flash_bwd_bf16(const void*, const void*, const void*, const void*, const vo
                     int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int64_t, int, int, int, int, int, float, float, uint64_t, int,
-                    int, const float*, hipStream_t);
+                    int, const float*, int, hipStream_t);
 void attn_dropout_apply_bf16(void*, int64_t, int64_t, int64_t, float, uint64_t,
                              hipStream_t);
 void attn_dropout_apply_f32(void*, int64_t, int64_t, int64_t, float, uint64_t,
@@ -120,13 +121,14 @@ void gemm_dw_bf16(const void*, const void*, float*, void*, int, int64_t, int64_t
 void flash_decode_bf16(const void*, const void*, const void*, void*, const int*,
                        int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                        int64_t, int64_t, int64_t, int64_t, int, int, int, int,
-                       float, int, const float*, hipStream_t);
+                       float, int, const float*, int, hipStream_t);
 int flash_decode_num_splits(int, int, int);
 void flash_decode_split_bf16(const void*, const void*, const void*, void*,
                              float*, float*, float*, const int*, int64_t,
                              int64_t, int64_t, int64_t, int64_t, int64_t,
                              int64_t, int64_t, int64_t, int64_t, int, int, int,
-                             int, int, float, int, const float*, hipStream_t);
+                             int, int, float, int, const float*, int,
+                             hipStream_t);
 void rope_fwd_bf16(const void*, void*, const float*, const float*, int64_t, int64_t,
                    int64_t, int64_t, int64_t, int64_t, int, int, int, int, int,
                    hipStream_t);
@@ -426,12 +428,25 @@ static const float* alibi_slopes_ptr(const c10::optional<torch::Tensor>& slopes,
   return slopes->data_ptr<float>();
 }
 
+// sliding window (0 = off): query i sees key j iff j <= i and i - j < window.
+// Returns the kernel argument, clamped to the key count (the same mask).
+static int window_arg(int64_t window, bool causal, bool has_alibi, int64_t Sk,
+                      const char* op) {
+  TORCH_CHECK(window >= 0, op, ": window must be >= 0 (0 = off)");
+  if (window == 0) return 0;
+  TORCH_CHECK(causal, op, ": a sliding window requires causal attention");
+  TORCH_CHECK(!has_alibi, op,
+              ": a sliding window cannot be combined with alibi_slopes");
+  return (int)std::min<int64_t>(window, std::max<int64_t>(Sk, 1));
+}
+
 // ---------------------------------------------------------------------------
 // fused single-query decode attention (K16 serving path)
 // ---------------------------------------------------------------------------
 torch::Tensor flash_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                            double scale, c10::optional<torch::Tensor> kv_len,
-                           c10::optional<torch::Tensor> alibi_slopes) {
+                           c10::optional<torch::Tensor> alibi_slopes,
+                           int64_t window) {
   // q: [B, H, 1, D]; k/v: [B, Hkv, Skv, D] (the decode KV-cache layout)
   TORCH_CHECK(q.dim() == 4 && q.size(2) == 1, "flash_decode: q must be [B,H,1,D]");
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "flash_decode is bf16-only");
@@ -447,6 +462,8 @@ torch::Tensor flash_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
     kvl = kv_len->data_ptr<int>();
   }
   const float* slopes = alibi_slopes_ptr(alibi_slopes, q, H);
+  // decode is causal by construction: the query is the last cached key
+  const int win = window_arg(window, true, slopes != nullptr, Skv, "flash_decode");
   auto o = torch::empty({B, H, 1, D}, q.options());
   const int S = flash_decode_num_splits(B, H, Skv);
   if (S > 1) {
@@ -462,13 +479,13 @@ torch::Tensor flash_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
         pm.data_ptr<float>(), pl.data_ptr<float>(), pa.data_ptr<float>(), kvl,
         q.stride(0), q.stride(1), k.stride(0), k.stride(2), k.stride(1),
         v.stride(0), v.stride(2), v.stride(1), o.stride(0), o.stride(1), B, H,
-        S, Skv, D, (float)scale, H / Hkv, slopes, cur_stream());
+        S, Skv, D, (float)scale, H / Hkv, slopes, win, cur_stream());
   } else {
     flash_decode_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                       kvl, q.stride(0), q.stride(1), k.stride(0), k.stride(2),
                       k.stride(1), v.stride(0), v.stride(2), v.stride(1),
                       o.stride(0), o.stride(1), B, H, Skv, D, (float)scale,
-                      H / Hkv, slopes, cur_stream());
+                      H / Hkv, slopes, win, cur_stream());
   }
   check_launch("flash_decode");
   return o;
@@ -528,7 +545,8 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
                                                    double p_drop, int64_t seed,
                                                    bool causal,
                                                    c10::optional<torch::Tensor> kv_len,
-                                                   c10::optional<torch::Tensor> alibi_slopes) {
+                                                   c10::optional<torch::Tensor> alibi_slopes,
+                                                   int64_t window) {
   const int* kvl = nullptr;
   if (kv_len.has_value()) {
     TORCH_CHECK(kv_len->scalar_type() == torch::kInt32 && kv_len->is_cuda() &&
@@ -550,6 +568,8 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
               "GQA head counts: H divisible by Hkv, v matches k");
   const int kv_group = H / Hkv;
   const float* slopes = alibi_slopes_ptr(alibi_slopes, q, H);
+  const int win = window_arg(window, causal, slopes != nullptr, Sk, "flash_fwd");
+  TORCH_CHECK(win == 0 || Sq == Sk, "flash_fwd: a sliding window needs Sq == Sk");
   auto o = torch::empty({B, Sq, H, D}, q.options());
   auto lse = torch::empty({B, H, Sq}, q.options().dtype(torch::kFloat32));
   flash_fwd_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
@@ -557,7 +577,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
                  k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1),
                  v.stride(2), o.stride(0), o.stride(1), o.stride(2), B, H, Sq, Sk, D,
                  (float)scale, (float)p_drop, (uint64_t)seed, causal ? 1 : 0,
-                 kv_group, slopes, cur_stream());
+                 kv_group, slopes, win, cur_stream());
   check_launch("flash_fwd");
   return {o, lse};
 }
@@ -567,7 +587,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> flash_bwd(
     torch::Tensor dout, torch::Tensor lse, double scale, double p_drop, int64_t seed,
     bool causal, c10::optional<torch::Tensor> dqkv,
     c10::optional<torch::Tensor> kv_len,
-    c10::optional<torch::Tensor> alibi_slopes) {
+    c10::optional<torch::Tensor> alibi_slopes, int64_t window) {
   const int* kvl = nullptr;
   if (kv_len.has_value()) {
     TORCH_CHECK(kv_len->scalar_type() == torch::kInt32 && kv_len->is_cuda() &&
@@ -580,6 +600,8 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> flash_bwd(
   const int Sk = (int)k.size(1), Hkv = (int)k.size(2);
   const int kv_group = H / Hkv;
   const float* slopes = alibi_slopes_ptr(alibi_slopes, q, H);
+  const int win = window_arg(window, causal, slopes != nullptr, Sk, "flash_bwd");
+  TORCH_CHECK(win == 0 || Sq == Sk, "flash_bwd: a sliding window needs Sq == Sk");
   TORCH_CHECK(dout.is_contiguous() && o.is_contiguous());
   torch::Tensor dq, dk, dv;
   if (dqkv.has_value()) {
@@ -603,7 +625,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> flash_bwd(
       o.stride(2), dout.stride(0), dout.stride(1), dout.stride(2), dq.stride(0),
       dq.stride(1), dq.stride(2), dk.stride(0), dk.stride(1), dk.stride(2),
       dv.stride(0), dv.stride(1), dv.stride(2), B, H, Sq, Sk, D, (float)scale,
-      (float)p_drop, (uint64_t)seed, causal ? 1 : 0, kv_group, slopes,
+      (float)p_drop, (uint64_t)seed, causal ? 1 : 0, kv_group, slopes, win,
       cur_stream());
   check_launch("flash_bwd");
   return {dq, dk, dv};
@@ -773,16 +795,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_dw", &gemm_dw);
   m.def("flash_decode", &flash_decode, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("scale"), py::arg("kv_len"),
-        py::arg("alibi_slopes") = py::none());
+        py::arg("alibi_slopes") = py::none(), py::arg("window") = 0);
   m.def("embedding_fwd", &embedding_fwd);
   m.def("embedding_bwd", &embedding_bwd);
   m.def("flash_fwd", &flash_fwd, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("scale"), py::arg("p_drop"), py::arg("seed"), py::arg("causal"),
-        py::arg("kv_len"), py::arg("alibi_slopes") = py::none());
+        py::arg("kv_len"), py::arg("alibi_slopes") = py::none(), py::arg("window") = 0);
   m.def("flash_bwd", &flash_bwd, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o"), py::arg("dout"), py::arg("lse"), py::arg("scale"),
         py::arg("p_drop"), py::arg("seed"), py::arg("causal"), py::arg("dqkv"),
-        py::arg("kv_len"), py::arg("alibi_slopes") = py::none());
+        py::arg("kv_len"), py::arg("alibi_slopes") = py::none(), py::arg("window") = 0);
   m.def("attn_dropout_apply", &attn_dropout_apply);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);

@@ -191,7 +191,12 @@ __device__ __forceinline__ float drop_keep(uint64_t seed, uint64_t bh, int64_t S
 // row-shift-equivalent to BLOOM's slope * kv under softmax, is bounded by the
 // sequence length and is <= 0 under the causal mask.  The ALIBI=false
 // instantiations never touch the pointer.
-template <int D, bool ALIBI>
+// WINDOW: compile-time variant for causal sliding-window attention: query i
+// sees key j iff j <= i and i - j < window (window keys, the query's own
+// included).  Besides the in-register predicate, the kv loops skip every tile
+// that lies entirely below the band, so a q block reads about window + QBLK
+// keys.  The WINDOW=false instantiations never read `window`.
+template <int D, bool ALIBI, bool WINDOW>
 __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, bf16_t* __restrict__ o, float* __restrict__ lse,
@@ -199,7 +204,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss,
     int64_t v_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh, int H, int Sq, int Sk,
     float scale, float p_drop, uint64_t seed, int causal, int kv_group,
-    const float* __restrict__ alibi_slopes) {
+    const float* __restrict__ alibi_slopes, int window) {
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
 
@@ -257,7 +262,12 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
   float slope2 = 0.f;
   if constexpr (ALIBI) slope2 = alibi_slopes[h] * 1.4426950408889634f;
 
-  for (int round = 0; round < n_rounds; ++round) {
+  // sliding window: the first staging round is the one holding the lowest
+  // key any query of this block can see (uniform across the workgroup)
+  int round0 = 0;
+  if constexpr (WINDOW) round0 = max(0, q_block - window + 1) / (2 * KVB);
+
+  for (int round = round0; round < n_rounds; ++round) {
     const int kvR = round * 2 * KVB;
     __syncthreads();
     stage_tile<2 * KVB, D, true, false>(k_lds, nullptr, kp, kvR, Sk, k_ss, tid);
@@ -268,6 +278,9 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     const int kv0 = kvR + sub * KVB;
     const int ro = sub * KVB;  // row offset inside the staged images
     if (kv0 >= kv_end || (causal && kv0 > q_base + QB - 1)) continue;
+    if constexpr (WINDOW) {  // sub-tile entirely below this wave's band
+      if (kv0 + KVB - 1 < q_base - window + 1) continue;
+    }
 
     // S = K x Q^T : two 32x32 tiles
     f32x16_t s0{}, s1{};
@@ -300,6 +313,10 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
       }
       if (kva >= sk_eff || (causal && kva > qg)) a = -3.0e38f;
       if (kvb >= sk_eff || (causal && kvb > qg)) bb = -3.0e38f;
+      if constexpr (WINDOW) {
+        if (qg - kva >= window) a = -3.0e38f;
+        if (qg - kvb >= window) bb = -3.0e38f;
+      }
       sv[0][r] = a;
       sv[1][r] = bb;
       pmax = fmaxf(pmax, fmaxf(a, bb));
@@ -428,8 +445,11 @@ __global__ void rowdot_kernel(const bf16_t* __restrict__ dout,
 // takes 202 VGPRs with no scratch and measured faster on MI355X (b4 s1024 h16
 // fwd+bwd 293 us vs 333 us, profiles/alibi_flash.md).  The non-ALiBi
 // instantiation keeps its target.
-template <int D, bool ALIBI>
-__global__ __launch_bounds__(256, D == 64 ? (ALIBI ? 2 : BWD_KV_OCC)
+// The D=64 sliding-window instantiation targets 2 waves/SIMD for the same
+// reason: at 3 its extra compares raise the scratch to 76 B/lane, above the
+// 64 B of the plain build; at 2 it takes 204 VGPRs with no scratch.
+template <int D, bool ALIBI, bool WINDOW>
+__global__ __launch_bounds__(256, D == 64 ? ((ALIBI || WINDOW) ? 2 : BWD_KV_OCC)
                                           : 2) void flash_bwd_kv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
@@ -440,7 +460,8 @@ __global__ __launch_bounds__(256, D == 64 ? (ALIBI ? 2 : BWD_KV_OCC)
     int64_t v_ss, int64_t v_sh, int64_t do_sb, int64_t do_ss, int64_t do_sh,
     int64_t dk_sb, int64_t dk_ss, int64_t dk_sh, int64_t dv_sb, int64_t dv_ss,
     int64_t dv_sh, int H, int Sq, int Sk, float scale, float p_drop, uint64_t seed,
-    int causal, int kv_group, const float* __restrict__ alibi_slopes) {
+    int causal, int kv_group, const float* __restrict__ alibi_slopes,
+    int window) {
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
   // D=64: 64-row staging tiles + persistent K/V fragments.  D=128: 32-row
@@ -500,7 +521,13 @@ __global__ __launch_bounds__(256, D == 64 ? (ALIBI ? 2 : BWD_KV_OCC)
   // fully-padded kv block: accumulators stay zero, skip straight to the
   // (zero) writes.  kv_block is uniform across the block, so this does not
   // break the __syncthreads inside the loop.
-  const int n_qtiles = (kv_block < sk_eff) ? CDIV(Sq, QTILE) : 0;
+  // sliding window: the last query that sees a key of this block is
+  // kv_block + QBLK - 1 + window - 1, so the q-tile loop stops after the tile
+  // holding it (uniform across the workgroup; the launcher clamps window to
+  // the sequence length, so the sum cannot overflow)
+  int q_hi = Sq;
+  if constexpr (WINDOW) q_hi = min(Sq, kv_block + QBLK + window - 1);
+  const int n_qtiles = (kv_block < sk_eff) ? CDIV(q_hi, QTILE) : 0;
 
   for (int g = 0; g < kv_group; ++g) {
   const int h = hk * kv_group + g;
@@ -525,6 +552,9 @@ __global__ __launch_bounds__(256, D == 64 ? (ALIBI ? 2 : BWD_KV_OCC)
 
   auto compute_tile = [&](int buf, int q0) {
     if (causal && q0 + QTILE - 1 < kv_base) return;  // entirely above diag
+    if constexpr (WINDOW) {  // entirely below this wave's band
+      if (q0 - (kv_base + QB - 1) >= window) return;
+    }
 
 #pragma unroll
     for (int sub_i = 0; sub_i < NSUB; ++sub_i) {
@@ -537,6 +567,9 @@ __global__ __launch_bounds__(256, D == 64 ? (ALIBI ? 2 : BWD_KV_OCC)
 #endif
       const int q0s = q0 + sub * QB;
       if (causal && q0s + QB - 1 < kv_base) continue;
+      if constexpr (WINDOW) {
+        if (q0s - (kv_base + QB - 1) >= window) continue;
+      }
       const int ro = sub * QB;  // row offset inside the staged images
 
       // S[q][kv] = Q x K^T  (lane col = kv)
@@ -583,8 +616,9 @@ __global__ __launch_bounds__(256, D == 64 ? (ALIBI ? 2 : BWD_KV_OCC)
             const int k = r4 * 4 + j;
             const int r = c16 * 8 + k;
             const int qrow = qbase + j;
-            const bool valid =
+            bool valid =
                 qrow < Sq && kvg < sk_eff && (!causal || qrow >= kvg);
+            if constexpr (WINDOW) valid = valid && (qrow - kvg < window);
             float p = 0.f;
             float sc = s[r] * scale;
             // (kv - q) is recomputed per element: nothing extra stays live
@@ -668,7 +702,7 @@ __global__ __launch_bounds__(256, D == 64 ? (ALIBI ? 2 : BWD_KV_OCC)
 // ===========================================================================
 // backward over q tiles: dQ   (block = 128 q rows, wave owns 32; fwd-like)
 // ===========================================================================
-template <int D, bool ALIBI>
+template <int D, bool ALIBI, bool WINDOW>
 __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
@@ -678,7 +712,8 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
     int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss, int64_t v_sh,
     int64_t do_sb, int64_t do_ss, int64_t do_sh, int64_t dq_sb, int64_t dq_ss,
     int64_t dq_sh, int H, int Sq, int Sk, float scale, float p_drop, uint64_t seed,
-    int causal, int kv_group, const float* __restrict__ alibi_slopes) {
+    int causal, int kv_group, const float* __restrict__ alibi_slopes,
+    int window) {
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
   constexpr int KVTILE = (D == 64) ? 2 * QB : QB;
@@ -739,7 +774,11 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
   const int kv_end = causal ? min(sk_eff, q_block + QBLK) : sk_eff;
   const int n_tiles = CDIV(kv_end, KVTILE);
 
-  for (int tile = 0; tile < n_tiles; ++tile) {
+  // sliding window: start at the tile holding the block's lowest visible key
+  int tile0 = 0;
+  if constexpr (WINDOW) tile0 = max(0, q_block - window + 1) / KVTILE;
+
+  for (int tile = tile0; tile < n_tiles; ++tile) {
     const int kv0 = tile * KVTILE;
     __syncthreads();
     stage_tile<KVTILE, D, true, true>(k_row, k_tr, kp, kv0, Sk, k_ss, tid);
@@ -752,6 +791,9 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
     for (int sub = 0; sub < NSUB; ++sub) {
       const int kv0s = kv0 + sub * QB;
       if (kv0s >= kv_end || (causal && kv0s > q_base + QB - 1)) continue;
+      if constexpr (WINDOW) {  // sub-tile entirely below this wave's band
+        if (kv0s + QB - 1 < q_base - window + 1) continue;
+      }
       const int ro = sub * QB;
 
       // S^T[kv][q] = K x Q^T ;  dPd^T[kv][q] = V x dO^T   (lane col = q)
@@ -782,7 +824,8 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
         for (int j = 0; j < 4; ++j) {
           const int r = r4 * 4 + j;
           const int kv = kvb + j;
-          const bool valid = kv < sk_eff && qg < Sq && (!causal || kv <= qg);
+          bool valid = kv < sk_eff && qg < Sq && (!causal || kv <= qg);
+          if constexpr (WINDOW) valid = valid && (qg - kv < window);
           float sc = st[r] * scale;
           if constexpr (ALIBI) sc = fmaf(slope, rel0 + (float)(8 * r4 + j), sc);
           float p = valid ? __expf(sc - lse_lane) : 0.f;
@@ -852,24 +895,30 @@ extern "C" void flash_fwd_bf16(const void* q, const void* k, const void* v, void
                                int64_t o_sh, int B, int H, int Sq, int Sk, int D,
                                float scale, float p_drop, uint64_t seed, int causal,
                                int kv_group, const float* alibi_slopes,
-                               hipStream_t stream) {
+                               int window, hipStream_t stream) {
   dim3 grid(CDIV(Sq, QBLK), B * H);
   dim3 block(256);
 #define FWD_ARGS                                                                     \
   (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, kv_len,     \
       q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, o_sb, o_ss, o_sh, H, Sq, \
-      Sk, scale, p_drop, seed, causal, kv_group, alibi_slopes
+      Sk, scale, p_drop, seed, causal, kv_group, alibi_slopes, window
+  // the binding rejects window together with ALiBi: no cross product
   const bool alibi = alibi_slopes != nullptr;
+  window = window > 0 ? min(window, max(Sq, Sk)) : 0;  // same mask, no overflow
   if (D == 64) {
     if (alibi)
-      flash_fwd_kernel<64, true><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<64, true, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+    else if (window > 0)
+      flash_fwd_kernel<64, false, true><<<grid, block, 0, stream>>>(FWD_ARGS);
     else
-      flash_fwd_kernel<64, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<64, false, false><<<grid, block, 0, stream>>>(FWD_ARGS);
   } else if (D == 128) {
     if (alibi)
-      flash_fwd_kernel<128, true><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<128, true, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+    else if (window > 0)
+      flash_fwd_kernel<128, false, true><<<grid, block, 0, stream>>>(FWD_ARGS);
     else
-      flash_fwd_kernel<128, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<128, false, false><<<grid, block, 0, stream>>>(FWD_ARGS);
   }
 #undef FWD_ARGS
 }
@@ -884,7 +933,7 @@ extern "C" void flash_bwd_bf16(
     int64_t dq_ss, int64_t dq_sh, int64_t dk_sb, int64_t dk_ss, int64_t dk_sh,
     int64_t dv_sb, int64_t dv_ss, int64_t dv_sh, int B, int H, int Sq, int Sk, int D,
     float scale, float p_drop, uint64_t seed, int causal, int kv_group,
-    const float* alibi_slopes, hipStream_t stream) {
+    const float* alibi_slopes, int window, hipStream_t stream) {
   // Drow = rowsum(dO * O)  (dO and O share layout; use dO's strides for both:
   // the wrapper guarantees o was allocated with the same layout)
   {
@@ -905,27 +954,31 @@ extern "C" void flash_bwd_bf16(
   (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse,    \
       drow_ws, kv_len, (bf16_t*)dk, (bf16_t*)dv, q_sb, q_ss, q_sh, k_sb, k_ss,       \
       k_sh, v_sb, v_ss, v_sh, do_sb, do_ss, do_sh, dk_sb, dk_ss, dk_sh, dv_sb,       \
-      dv_ss, dv_sh, H, Sq, Sk, scale, p_drop, seed, causal, kv_group, alibi_slopes
+      dv_ss, dv_sh, H, Sq, Sk, scale, p_drop, seed, causal, kv_group,                \
+      alibi_slopes, window
 #define BWD_ARGS_Q                                                                   \
   (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse,    \
       drow_ws, kv_len, (bf16_t*)dq, q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss,  \
       v_sh, do_sb, do_ss, do_sh, dq_sb, dq_ss, dq_sh, H, Sq, Sk, scale, p_drop,      \
-      seed, causal, kv_group, alibi_slopes
+      seed, causal, kv_group, alibi_slopes, window
   dim3 block(256);
   const int Hkv = H / kv_group;  // bwd_kv grid spans the KV heads
   const dim3 grid_kv(CDIV(Sk, QBLK), B * Hkv), grid_q(CDIV(Sq, QBLK), B * H);
-#define BWD_LAUNCH(DD, AL)                                                           \
+#define BWD_LAUNCH(DD, AL, WIN)                                                      \
   do {                                                                               \
-    flash_bwd_kv_kernel<DD, AL><<<grid_kv, block, 0, stream>>>(BWD_ARGS_KV);         \
-    flash_bwd_q_kernel<DD, AL><<<grid_q, block, 0, stream>>>(BWD_ARGS_Q);            \
+    flash_bwd_kv_kernel<DD, AL, WIN><<<grid_kv, block, 0, stream>>>(BWD_ARGS_KV);    \
+    flash_bwd_q_kernel<DD, AL, WIN><<<grid_q, block, 0, stream>>>(BWD_ARGS_Q);       \
   } while (0)
   const bool alibi = alibi_slopes != nullptr;
+  window = window > 0 ? min(window, max(Sq, Sk)) : 0;  // same mask, no overflow
   if (D == 64) {
-    if (alibi) BWD_LAUNCH(64, true);
-    else BWD_LAUNCH(64, false);
+    if (alibi) BWD_LAUNCH(64, true, false);
+    else if (window > 0) BWD_LAUNCH(64, false, true);
+    else BWD_LAUNCH(64, false, false);
   } else if (D == 128) {
-    if (alibi) BWD_LAUNCH(128, true);
-    else BWD_LAUNCH(128, false);
+    if (alibi) BWD_LAUNCH(128, true, false);
+    else if (window > 0) BWD_LAUNCH(128, false, true);
+    else BWD_LAUNCH(128, false, false);
   }
 #undef BWD_LAUNCH
 }

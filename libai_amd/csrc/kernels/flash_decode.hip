@@ -22,14 +22,18 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 // ALIBI: compile-time variant adding slope[h] * (key - qpos) to each score,
 // qpos = kv_len[b] - 1 (the new token is the last cached key).  Same (kv - q)
 // form as the training kernels; one fp32 slope per QUERY head.
-template <int D, bool ALIBI>
+// WINDOW: compile-time sliding-window variant: the query (at skv - 1) sees
+// the keys [max(0, skv - window), skv).  64-key chunks that end below the
+// window start are skipped whole (wave-uniform); keys below it inside a
+// straddling chunk get the sentinel (p = 0; the V loop is left as it is).
+template <int D, bool ALIBI, bool WINDOW>
 __global__ __launch_bounds__(256, 4) void flash_decode_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, bf16_t* __restrict__ o,
     const int* __restrict__ kv_len, int64_t q_sb, int64_t q_sh, int64_t k_sb,
     int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss, int64_t v_sh,
     int64_t o_sb, int64_t o_sh, int H, int Skv, float scale, int kv_group,
-    const float* __restrict__ alibi_slopes) {
+    const float* __restrict__ alibi_slopes, int window) {
   constexpr int DPL = D / 64;  // dims per lane
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -41,6 +45,8 @@ __global__ __launch_bounds__(256, 4) void flash_decode_kernel(
   const int skv = (kv_len != nullptr) ? kv_len[b] : Skv;
   float slope = 0.f;
   if constexpr (ALIBI) slope = alibi_slopes[h];
+  int win_lo = 0;  // first visible key
+  if constexpr (WINDOW) win_lo = max(0, skv - window);
 
   const bf16_t* qp = q + b * q_sb + h * q_sh;
   const bf16_t* kp = k + b * k_sb + hk * k_sh;
@@ -60,11 +66,17 @@ __global__ __launch_bounds__(256, 4) void flash_decode_kernel(
 #pragma unroll
   for (int t = 0; t < DPL; ++t) acc[t] = 0.f;
 
-  // each wave walks keys [wave*64 + chunk*256 ...)
-  for (int key0 = wave * 64; key0 < skv; key0 += 256) {
+  // each wave walks keys [wave*64 + chunk*256 ...); with a window it starts at
+  // its first 64-key chunk that does not end below win_lo
+  int chunk0 = wave;
+  if constexpr (WINDOW) {
+    const int c = win_lo >> 6;
+    chunk0 = c + ((wave - c) & 3);
+  }
+  for (int key0 = chunk0 * 64; key0 < skv; key0 += 256) {
     const int key = key0 + lane;
     float s = -3.0e38f;
-    if (key < skv) {
+    if (key < skv && (!WINDOW || key >= win_lo)) {
       const bf16_t* kr = kp + (int64_t)key * k_ss;
       float dot = 0.f;
 #pragma unroll
@@ -142,7 +154,11 @@ constexpr int SPLIT_KEYS = 512;
 // ALIBI: every split uses the SAME per-batch query position kv_len[b] - 1,
 // so the cross-split merge stays valid and the outputs stay bitwise
 // independent of the cache capacity.
-template <int D, bool ALIBI>
+// WINDOW: the split boundaries stay the fixed multiples of 512; a split that
+// ends at or below the window start takes the null-split exit, and the chunk
+// walk inside a split skips and masks exactly as the single-workgroup kernel
+// does, so the capacity independence holds with a window too.
+template <int D, bool ALIBI, bool WINDOW>
 __global__ __launch_bounds__(256, 4) void flash_decode_split_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, float* __restrict__ part_m,
@@ -150,7 +166,7 @@ __global__ __launch_bounds__(256, 4) void flash_decode_split_kernel(
     const int* __restrict__ kv_len, int64_t q_sb, int64_t q_sh, int64_t k_sb,
     int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss, int64_t v_sh,
     int H, int S, int Skv, float scale, int kv_group,
-    const float* __restrict__ alibi_slopes) {
+    const float* __restrict__ alibi_slopes, int window) {
   constexpr int DPL = D / 64;
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -165,8 +181,11 @@ __global__ __launch_bounds__(256, 4) void flash_decode_split_kernel(
   const int lo = split * SPLIT_KEYS;
   const int hi = min(lo + SPLIT_KEYS, skv);
   const int64_t pidx = (int64_t)bh * S + split;
+  int win_lo = 0;  // first visible key
+  if constexpr (WINDOW) win_lo = max(0, skv - window);
 
-  if (lo >= skv) {  // null split: exact no-op under the merge
+  // null split: exact no-op under the merge
+  if (lo >= skv || (WINDOW && lo + SPLIT_KEYS <= win_lo)) {
     if (tid == 0) {
       part_m[pidx] = -3.0e38f;
       part_l[pidx] = 0.f;
@@ -197,10 +216,16 @@ __global__ __launch_bounds__(256, 4) void flash_decode_split_kernel(
 #pragma unroll
   for (int t = 0; t < DPL; ++t) acc[t] = 0.f;
 
-  for (int key0 = lo + wave * 64; key0 < hi; key0 += 256) {
+  // same walk as the single-workgroup kernel, relative to the split start
+  int chunk0 = wave;
+  if constexpr (WINDOW) {
+    const int c = max(0, win_lo - lo) >> 6;
+    chunk0 = c + ((wave - c) & 3);
+  }
+  for (int key0 = lo + chunk0 * 64; key0 < hi; key0 += 256) {
     const int key = key0 + lane;
     float s = -3.0e38f;
-    if (key < hi) {
+    if (key < hi && (!WINDOW || key >= win_lo)) {
       const bf16_t* kr = kp + (int64_t)key * k_ss;
       float dot = 0.f;
 #pragma unroll
@@ -312,24 +337,26 @@ extern "C" void flash_decode_bf16(const void* q, const void* k, const void* v,
                                   int64_t v_sh, int64_t o_sb, int64_t o_sh, int B,
                                   int H, int Skv, int D, float scale,
                                   int kv_group, const float* alibi_slopes,
-                                  hipStream_t stream) {
+                                  int window, hipStream_t stream) {
   dim3 grid(B * H);
 #define DECODE_ARGS                                                            \
   (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, kv_len,    \
       q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, o_sb, o_sh, H, Skv,      \
-      scale, kv_group, alibi_slopes
+      scale, kv_group, alibi_slopes, window
+#define DECODE_LAUNCH(DD, AL, WIN) \
+  flash_decode_kernel<DD, AL, WIN><<<grid, dim3(256), 0, stream>>>(DECODE_ARGS)
+  // the binding rejects window together with ALiBi: no cross product
   const bool alibi = alibi_slopes != nullptr;
   if (D == 64) {
-    if (alibi)
-      flash_decode_kernel<64, true><<<grid, dim3(256), 0, stream>>>(DECODE_ARGS);
-    else
-      flash_decode_kernel<64, false><<<grid, dim3(256), 0, stream>>>(DECODE_ARGS);
+    if (alibi) DECODE_LAUNCH(64, true, false);
+    else if (window > 0) DECODE_LAUNCH(64, false, true);
+    else DECODE_LAUNCH(64, false, false);
   } else if (D == 128) {
-    if (alibi)
-      flash_decode_kernel<128, true><<<grid, dim3(256), 0, stream>>>(DECODE_ARGS);
-    else
-      flash_decode_kernel<128, false><<<grid, dim3(256), 0, stream>>>(DECODE_ARGS);
+    if (alibi) DECODE_LAUNCH(128, true, false);
+    else if (window > 0) DECODE_LAUNCH(128, false, true);
+    else DECODE_LAUNCH(128, false, false);
   }
+#undef DECODE_LAUNCH
 #undef DECODE_ARGS
 }
 
@@ -339,27 +366,29 @@ extern "C" void flash_decode_split_bf16(
     int64_t q_sh, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sb,
     int64_t v_ss, int64_t v_sh, int64_t o_sb, int64_t o_sh, int B, int H,
     int S, int Skv, int D, float scale, int kv_group, const float* alibi_slopes,
-    hipStream_t stream) {
+    int window, hipStream_t stream) {
   dim3 grid(B * H * S), mgrid(B * H);
 #define SPLIT_ARGS                                                             \
   (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, part_m, part_l,        \
       part_acc, kv_len, q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, H, S,  \
-      Skv, scale, kv_group, alibi_slopes
+      Skv, scale, kv_group, alibi_slopes, window
+#define SPLIT_LAUNCH(DD, AL, WIN)                                              \
+  flash_decode_split_kernel<DD, AL, WIN><<<grid, dim3(256), 0, stream>>>(      \
+      SPLIT_ARGS)
   const bool alibi = alibi_slopes != nullptr;
   if (D == 64) {
-    if (alibi)
-      flash_decode_split_kernel<64, true><<<grid, dim3(256), 0, stream>>>(SPLIT_ARGS);
-    else
-      flash_decode_split_kernel<64, false><<<grid, dim3(256), 0, stream>>>(SPLIT_ARGS);
+    if (alibi) SPLIT_LAUNCH(64, true, false);
+    else if (window > 0) SPLIT_LAUNCH(64, false, true);
+    else SPLIT_LAUNCH(64, false, false);
     flash_decode_merge_kernel<64><<<mgrid, dim3(64), 0, stream>>>(
         part_m, part_l, part_acc, (bf16_t*)o, H, S, o_sb, o_sh);
   } else if (D == 128) {
-    if (alibi)
-      flash_decode_split_kernel<128, true><<<grid, dim3(256), 0, stream>>>(SPLIT_ARGS);
-    else
-      flash_decode_split_kernel<128, false><<<grid, dim3(256), 0, stream>>>(SPLIT_ARGS);
+    if (alibi) SPLIT_LAUNCH(128, true, false);
+    else if (window > 0) SPLIT_LAUNCH(128, false, true);
+    else SPLIT_LAUNCH(128, false, false);
     flash_decode_merge_kernel<128><<<mgrid, dim3(64), 0, stream>>>(
         part_m, part_l, part_acc, (bf16_t*)o, H, S, o_sb, o_sh);
   }
+#undef SPLIT_LAUNCH
 #undef SPLIT_ARGS
 }

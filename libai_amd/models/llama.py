@@ -29,13 +29,19 @@ class LlamaAttention(nn.Module):
     projects/Qwen, projects/ChatGLM).  num_key_value_heads == num_heads is
     plain MHA with the fused qkv projection; fewer kv heads use a separate
     q projection + fused [k|v] pair, and the flash kernels map each query
-    head to kv head h // (Hq/Hkv) in-kernel."""
+    head to kv head h // (Hq/Hkv) in-kernel.
+
+    sliding_window=W (Mistral): causal attention over the last W keys, the
+    query's own included (HF's ``q_idx - kv_idx < sliding_window``); every
+    branch of forward honours it.  The KV cache keeps all keys."""
 
     def __init__(self, hidden_size, num_heads, max_position_embeddings,
                  init_method, output_init_method, rope_theta=10000.0,
-                 num_key_value_heads=None, sequence_parallel=False, *,
-                 layer_idx=0):
+                 num_key_value_heads=None, sequence_parallel=False,
+                 sliding_window=None, *, layer_idx=0):
         super().__init__()
+        assert sliding_window is None or sliding_window >= 0, sliding_window
+        self.sliding_window = sliding_window or None  # None/0 = off
         self.sequence_parallel = sequence_parallel
         self.hidden_size = hidden_size
         self.num_heads = num_heads
@@ -106,7 +112,8 @@ class LlamaAttention(nn.Module):
             cos_t, sin_t = _tables(self.max_pos, self.head_dim,
                                    self.rope_theta, hidden_states.device)
             qo = ext().rope_kv_insert(q, k, v, ck, cv, cos_t, sin_t, position, True)
-            ctx = flash_decode_attn(qo, ck, cv, self.scale, kv_len=kv32)
+            ctx = flash_decode_attn(qo, ck, cv, self.scale, kv_len=kv32,
+                                    window=self.sliding_window)
             context = ctx.permute(0, 2, 1, 3).reshape(
                 b, 1, self.num_heads_local * self.head_dim)
             out, _ = self.o_proj(context)
@@ -122,14 +129,22 @@ class LlamaAttention(nn.Module):
         q = apply_rotary_pos_emb(q, self.max_pos, self.rope_theta, pos0)
         k = apply_rotary_pos_emb(k, self.max_pos, self.rope_theta, pos0)
 
+        window = self.sliding_window
         if (
             past_key_value is None
-            and not use_cache
+            # a windowed model also runs its prompt pass (use_cache) here, so
+            # a long prefill never materializes S x S scores
+            and (not use_cache or window is not None)
             and flash_attention_available(self.head_dim, q.dtype, q.device, s, s, None)
         ):
             o = flash_attention(q, k, v, self.scale, p_drop=0.0, causal=True,
-                                training=self.training)
+                                training=self.training, window=window)
             context = o.reshape(b, s, self.num_heads_local * self.head_dim)
+            if use_cache:  # the cache gets every key, in [b, kvh, s, hd]
+                present = (k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3))
+                out, _ = self.o_proj(context)
+                out = out + residual if residual is not None else out
+                return out, present
         else:
             # unfused path (decode / CPU): [b, nh, s, hs]
             group = self.num_heads_local // self.num_kv_local
@@ -150,7 +165,8 @@ class LlamaAttention(nn.Module):
                 qh, self.head_dim
             ):
                 # fused single-token decode (K16); GQA mapping in-kernel
-                ctx = flash_decode_attn(qh.contiguous(), kh, vh, self.scale)
+                ctx = flash_decode_attn(qh.contiguous(), kh, vh, self.scale,
+                                        window=window)
                 context = ctx.permute(0, 2, 1, 3).reshape(
                     b, 1, self.num_heads_local * self.head_dim)
                 out, _ = self.o_proj(context)
@@ -161,7 +177,16 @@ class LlamaAttention(nn.Module):
                 vh = vh.repeat_interleave(group, dim=1)
             scores = torch.matmul(qh, kh.transpose(-1, -2))
             causal = past_key_value is None
-            probs = fused_scale_mask_softmax(scores, scale=self.scale, causal=causal,
+            band = None
+            if window is not None:
+                # [b, sq, sk] bool, true = masked: query pos0 + i must not see
+                # key j once (pos0 + i) - j >= W (on top of the causal mask)
+                sk = kh.shape[2]
+                qi = torch.arange(pos0, pos0 + s, device=q.device)[:, None]
+                kj = torch.arange(sk, device=q.device)[None, :]
+                band = ((qi - kj) >= window)[None].expand(b, s, sk)
+            probs = fused_scale_mask_softmax(scores, band, scale=self.scale,
+                                             causal=causal,
                                              training=self.training)
             ctx = torch.matmul(probs, vh)
             context = ctx.permute(0, 2, 1, 3).reshape(
@@ -205,8 +230,8 @@ class LlamaDecoderLayer(nn.Module):
     def __init__(self, hidden_size, intermediate_size, num_heads,
                  max_position_embeddings, rms_norm_eps, init_method,
                  output_init_method, rope_theta=10000.0,
-                 num_key_value_heads=None, sequence_parallel=False, *,
-                 layer_idx=0):
+                 num_key_value_heads=None, sequence_parallel=False,
+                 sliding_window=None, *, layer_idx=0):
         super().__init__()
         self.layer_idx = layer_idx
         self.input_layernorm = RMSLayerNorm(hidden_size, eps=rms_norm_eps,
@@ -216,6 +241,7 @@ class LlamaDecoderLayer(nn.Module):
                                         output_init_method, rope_theta,
                                         num_key_value_heads,
                                         sequence_parallel=sequence_parallel,
+                                        sliding_window=sliding_window,
                                         layer_idx=layer_idx)
         self.post_attention_layernorm = RMSLayerNorm(hidden_size, eps=rms_norm_eps,
                                                      layer_idx=layer_idx)
@@ -277,9 +303,11 @@ class LlamaModel(nn.Module):
         num_key_value_heads=None,
         sequence_parallel=False,
         amp_enabled=False,
+        sliding_window=None,
     ):
         super().__init__()
         self.sequence_parallel = sequence_parallel
+        self.sliding_window = sliding_window or None
         init_method = init_method_normal(initializer_range)
         output_init_method = (
             scaled_init_method_normal(initializer_range, hidden_layers)
@@ -295,6 +323,7 @@ class LlamaModel(nn.Module):
                     max_position_embeddings, rms_norm_eps, init_method,
                     output_init_method, rope_theta, num_key_value_heads,
                     sequence_parallel=sequence_parallel,
+                    sliding_window=sliding_window,
                     layer_idx=i,
                 )
                 for i in range(hidden_layers)
@@ -326,6 +355,7 @@ class LlamaModel(nn.Module):
             "num_key_value_heads": cfg.get("num_key_value_heads", None),
             "sequence_parallel": cfg.get("sequence_parallel", False),
             "amp_enabled": cfg.get("amp_enabled", False),
+            "sliding_window": cfg.get("sliding_window", None),
         }
 
     def _run_layer(self, layer, h, past=None, use_cache=False):

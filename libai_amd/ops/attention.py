@@ -13,6 +13,12 @@ the call) makes the kernels add slope[h] * (kv - q) to every pre-softmax
 score in-register — no bias tensor in HBM and, the slopes being constants, no
 bias gradient.  (kv - q) is row-shift-equivalent to BLOOM's slope * kv.
 
+Sliding window (Mistral): an optional integer ``window`` W >= 1 restricts
+causal attention to the last W keys, the query's own included (query i sees
+key j iff j <= i and i - j < W, HF's ``q_idx - kv_idx < sliding_window``).
+The kernels mask in-register and skip every tile below the band.  ``None`` or
+0 means off; a window covering the whole sequence is normalized to off.
+
 Replaces the reference's K2-K5 chain (reference
 libai/layers/attention.py:211-253).
 """
@@ -39,6 +45,21 @@ def bias_alibi_slopes(position_bias):
     return getattr(position_bias, "_alibi_slopes", None)
 
 
+def _window_arg(window, n_keys, causal=True, alibi_slopes=None):
+    """Kernel argument for a sliding window: 0 = off.  A window that covers
+    all n_keys keys masks nothing and runs the windowless instantiation."""
+    if window is None or window == 0:
+        return 0
+    window = int(window)
+    if window < 0:
+        raise ValueError(f"window must be >= 1 (or None/0 for off), got {window}")
+    if not causal:
+        raise ValueError("a sliding window requires causal attention")
+    if alibi_slopes is not None:
+        raise ValueError("a sliding window cannot be combined with alibi_slopes")
+    return 0 if window >= n_keys else window
+
+
 def flash_attention_available(head_dim, dtype, device, sq, sk, pad_mask):
     return (
         device.type == "cuda"
@@ -59,16 +80,18 @@ class _FlashAttnQKVFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, qkv5, scale, p_drop, causal, kv_len, alibi_slopes=None):
+    def forward(ctx, qkv5, scale, p_drop, causal, kv_len, alibi_slopes=None,
+                window=0):
         q = qkv5[..., 0, :]
         k = qkv5[..., 1, :]
         v = qkv5[..., 2, :]
         seed = draw_seed() if p_drop > 0 else 0
         o, lse = ext().flash_fwd(q, k, v, scale, p_drop, seed, causal, kv_len,
-                                 alibi_slopes)
+                                 alibi_slopes, window)
         ctx.save_for_backward(qkv5, o, lse)
         ctx.kv_len = kv_len
         ctx.alibi_slopes = alibi_slopes  # constant: no grad flows to it
+        ctx.window = window
         ctx.meta = (scale, p_drop, seed, causal)
         return o
 
@@ -80,31 +103,35 @@ class _FlashAttnQKVFn(torch.autograd.Function):
         ext().flash_bwd(
             qkv5[..., 0, :], qkv5[..., 1, :], qkv5[..., 2, :], o, do.contiguous(),
             lse, scale, p_drop, seed, causal, dqkv, ctx.kv_len,
-            ctx.alibi_slopes,
+            ctx.alibi_slopes, ctx.window,
         )
-        return dqkv, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None
 
 
 def flash_attention_qkv(qkv5, scale, p_drop=0.0, causal=True, training=True,
-                        kv_len=None, alibi_slopes=None):
+                        kv_len=None, alibi_slopes=None, window=None):
     """qkv5: packed [B, S, H, 3, D] bf16 -> O [B, S, H, D] (zero-copy in/out).
 
     kv_len: optional int32 [B] — keys at/after kv_len[b] are masked out.
-    alibi_slopes: optional fp32 [H] — adds slope[h] * (kv - q) to the scores."""
+    alibi_slopes: optional fp32 [H] — adds slope[h] * (kv - q) to the scores.
+    window: optional int W — causal sliding window over the last W keys."""
+    window = _window_arg(window, qkv5.shape[1], causal, alibi_slopes)
     return _FlashAttnQKVFn.apply(qkv5, scale, p_drop if training else 0.0, causal,
-                                 kv_len, alibi_slopes)
+                                 kv_len, alibi_slopes, window)
 
 
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, scale, p_drop, causal, kv_len, alibi_slopes=None):
+    def forward(ctx, q, k, v, scale, p_drop, causal, kv_len, alibi_slopes=None,
+                window=0):
         # q, k, v: [B, S, H, D] (may be strided views of the fused qkv buffer)
         seed = draw_seed() if p_drop > 0 else 0
         o, lse = ext().flash_fwd(q, k, v, scale, p_drop, seed, causal, kv_len,
-                                 alibi_slopes)
+                                 alibi_slopes, window)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.kv_len = kv_len
         ctx.alibi_slopes = alibi_slopes
+        ctx.window = window
         ctx.meta = (scale, p_drop, seed, causal)
         return o
 
@@ -114,18 +141,21 @@ class _FlashAttnFn(torch.autograd.Function):
         scale, p_drop, seed, causal = ctx.meta
         dq, dk, dv = ext().flash_bwd(
             q, k, v, o, do.contiguous(), lse, scale, p_drop, seed, causal, None,
-            ctx.kv_len, ctx.alibi_slopes,
+            ctx.kv_len, ctx.alibi_slopes, ctx.window,
         )
-        return dq, dk, dv, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 def flash_attention(q, k, v, scale, p_drop=0.0, causal=True, training=True,
-                    kv_len=None, alibi_slopes=None):
+                    kv_len=None, alibi_slopes=None, window=None):
     """q, k, v: [B, S, H, D] bf16 -> O [B, S, H, D].
 
-    alibi_slopes: optional fp32 [H] (query heads) — fused ALiBi bias."""
+    alibi_slopes: optional fp32 [H] (query heads) — fused ALiBi bias.
+    window: optional int W — causal sliding window: query i sees the keys
+    j <= i with i - j < W (not combinable with alibi_slopes or causal=False)."""
+    window = _window_arg(window, k.shape[1], causal, alibi_slopes)
     return _FlashAttnFn.apply(q, k, v, scale, p_drop if training else 0.0, causal,
-                              kv_len, alibi_slopes)
+                              kv_len, alibi_slopes, window)
 
 
 def decode_attention_available(q, head_dim):
@@ -139,7 +169,8 @@ def decode_attention_available(q, head_dim):
     )
 
 
-def flash_decode_attn(q, k, v, scale, kv_len=None, alibi_slopes=None):
+def flash_decode_attn(q, k, v, scale, kv_len=None, alibi_slopes=None,
+                      window=None):
     """q [B, H, 1, D], k/v [B, Hkv, Skv, D] (KV-cache layout) -> [B, H, 1, D].
 
     One fused kernel: online-softmax q.K^T -> .V, GQA head mapping in-kernel
@@ -147,5 +178,8 @@ def flash_decode_attn(q, k, v, scale, kv_len=None, alibi_slopes=None):
     flow._C.fused_multi_head_attention_inference_v2).
 
     alibi_slopes: optional fp32 [H] — adds slope[h] * (key - qpos) with the
-    query at the last valid key, qpos = kv_len[b] - 1 (Skv - 1 if no kv_len)."""
-    return ext().flash_decode(q, k, v, scale, kv_len, alibi_slopes)
+    query at the last valid key, qpos = kv_len[b] - 1 (Skv - 1 if no kv_len).
+    window: optional int W — only the last W valid keys are visible (and read):
+    [max(0, kv_len[b] - W), kv_len[b])."""
+    window = _window_arg(window, k.shape[2], True, alibi_slopes)
+    return ext().flash_decode(q, k, v, scale, kv_len, alibi_slopes, window)
