@@ -27,6 +27,14 @@ bool is_bf16(const torch::Tensor& t) {
   return t.scalar_type() == torch::kBFloat16;
 }
 
+// the bias kernels index rows in whole 16-byte vectors: a width that is not a
+// multiple of the vector width would read the wrong elements and leave the
+// tail columns unwritten (the Python wrappers route such widths elsewhere)
+void check_bias_width(const char* op, int W, int V) {
+  TORCH_CHECK(W % V == 0 && W >= V, op, ": width ", W,
+              " must be a positive multiple of the vector width ", V);
+}
+
 #define CHECK_IN(t)                                               \
   TORCH_CHECK(t.is_cuda(), #t " must be on device");              \
   TORCH_CHECK(t.is_contiguous(), #t " must be contiguous");
@@ -230,6 +238,7 @@ torch::Tensor bias_gelu_fwd(torch::Tensor x, c10::optional<torch::Tensor> b) {
   CHECK_IN(x);
   auto y = torch::empty_like(x);
   const int W = b.has_value() ? (int)b->numel() : (int)x.size(-1);
+  check_bias_width("bias_gelu_fwd", W, is_bf16(x) ? 8 : 4);
   auto fn = is_bf16(x) ? bias_gelu_fwd_bf16 : bias_gelu_fwd_f32;
   fn(x.data_ptr(), b.has_value() ? b->data_ptr() : nullptr, y.data_ptr(), x.numel(), W,
      cur_stream());
@@ -245,10 +254,11 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> bias_gelu_bwd(
   auto dx = torch::empty_like(x);
   const int W = b.has_value() ? (int)b->numel() : (int)x.size(-1);
   const int V = is_bf16(x) ? 8 : 4;
+  check_bias_width("bias_gelu_bwd", W, V);
   float* pp = nullptr;
   torch::Tensor partial;
   int P = 0;
-  if (want_dbias && W % V == 0) {
+  if (want_dbias) {
     P = bias_col_grid_rows(x.numel(), W, V);
     partial = torch::empty({P, W}, x.options().dtype(torch::kFloat32));
     pp = partial.data_ptr<float>();
@@ -284,6 +294,7 @@ torch::Tensor bias_dropout_res_fwd(torch::Tensor x, c10::optional<torch::Tensor>
   CHECK_IN(x);
   auto y = torch::empty_like(x);
   const int W = b.has_value() ? (int)b->numel() : (int)x.size(-1);
+  check_bias_width("bias_dropout_res_fwd", W, is_bf16(x) ? 8 : 4);
   auto fn = is_bf16(x) ? bias_dropout_res_fwd_bf16 : bias_dropout_res_fwd_f32;
   fn(x.data_ptr(), b.has_value() ? b->data_ptr() : nullptr,
      res.has_value() ? res->data_ptr() : nullptr, y.data_ptr(), x.numel(), W, (float)p,
@@ -298,9 +309,10 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> bias_dropout_res_bwd(
   auto dx = torch::empty_like(dy);
   const int W = (int)dy.size(-1);
   const int V = is_bf16(dy) ? 8 : 4;
+  check_bias_width("bias_dropout_res_bwd", W, V);
   float* pp = nullptr;
   torch::Tensor partial;
-  if (want_dbias && W % V == 0) {
+  if (want_dbias) {
     int P = bias_col_grid_rows(dy.numel(), W, V);
     partial = torch::empty({P, W}, dy.options().dtype(torch::kFloat32));
     pp = partial.data_ptr<float>();

@@ -2,7 +2,7 @@
 //
 // Replaces the reference's flow._C.fused_bias_add_gelu (libai/layers/mlp.py:95-97)
 // and flow._C.fused_bias_add_dropout (mlp.py:104-106, attention.py:265-267).
-// Memory-bound: 16-byte vectorized loads, fp32 math, philox-recomputed dropout
+// Memory-bound: 16-byte vectorized loads, fp32 math, hash-recomputed dropout
 // masks (no mask tensor traffic; backward regenerates the identical mask).
 #include "common.h"
 
@@ -61,12 +61,16 @@ __global__ void bias_gelu_kernel(const typename E::T* __restrict__ x,
 
 // ---------------------------------------------------------------------------
 // y = residual + dropout(x + b);  backward dx = dy * mask / (1-p)
-// mask is philox(seed, elem_idx) — identical in fwd and bwd.
+// mask is rnd_hash(seed, elem_idx / 4), byte elem_idx % 4 — identical in fwd
+// and bwd, and the same for bf16 and fp32.
 // ---------------------------------------------------------------------------
 // Dropout mask: one rnd_hash draw yields 4 byte-granular keep decisions
 // (p quantized to 1/256 like the attention dropout; a philox4 here cost ~60
 // VALU per 4 elements vs ~10 for the mixer).  fwd and bwd regenerate the
-// identical mask from (seed, element index).
+// identical mask from (seed, element index).  The keep rate is
+// (256 - thr8) / 256 while kept values are scaled by the unquantized
+// 1 / (1 - p), so E[keep * scale] is 0.9983 at p = 0.1, not 1.
+// Widths must be a multiple of the vector width (the bindings check it).
 template <class E, bool GRAD>
 __global__ void bias_dropout_res_kernel(const typename E::T* __restrict__ x,
                                         const typename E::T* __restrict__ b,

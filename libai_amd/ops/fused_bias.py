@@ -14,6 +14,27 @@ from ._ext import draw_seed, ext, use_hip
 __all__ = ["bias_gelu", "bias_dropout_add"]
 
 
+def _kernel_width(x, op):
+    """The kernels index rows in whole 16-byte vectors (8 bf16 / 4 fp32), so
+    they serve widths that are a multiple of 8.  Any other width runs the
+    composed torch path; this is a SHAPE fallback, not an extension fallback
+    -- log it once so it cannot hide silently."""
+    if x.shape[-1] > 0 and x.shape[-1] % 8 == 0:
+        return True
+    import logging
+
+    from ..utils.logger import log_first_n
+
+    log_first_n(
+        logging.WARNING,
+        f"{op}: width {x.shape[-1]} is not a multiple of 8; using the "
+        f"composed torch path for this shape",
+        n=1,
+        key=f"{op}_ragged_width",
+    )
+    return False
+
+
 class _BiasGeluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias):
@@ -33,7 +54,7 @@ class _BiasGeluFn(torch.autograd.Function):
             b = None
         dy = dy.contiguous()
         # the bias grad partials ride in the same kernel pass (no re-read
-        # of dx); falls back to the separate colsum for ragged widths
+        # of dx); ragged widths never get here (see _kernel_width)
         dx, dbias = ext().bias_gelu_bwd(x, b, dy, ctx.has_bias)
         if ctx.has_bias and dbias is None:
             dbias = ext().colsum(dx, x.shape[-1])
@@ -42,7 +63,7 @@ class _BiasGeluFn(torch.autograd.Function):
 
 def bias_gelu(x, bias=None):
     """y = gelu(x + bias) with exact-erf gelu (torch default)."""
-    if use_hip(x):
+    if use_hip(x) and _kernel_width(x, "bias_gelu"):
         return _BiasGeluFn.apply(x, bias)
     return F.gelu(x + bias if bias is not None else x)
 
@@ -79,7 +100,7 @@ class _BiasDropoutAddFn(torch.autograd.Function):
 
 def bias_dropout_add(x, bias=None, residual=None, p=0.0, training=True):
     """y = residual + dropout(x + bias).  Philox-recomputed mask (no mask tensor)."""
-    if use_hip(x):
+    if use_hip(x) and _kernel_width(x, "bias_dropout_add"):
         return _BiasDropoutAddFn.apply(x, bias, residual, p if training else 0.0)
     out = x + bias if bias is not None else x
     out = F.dropout(out, p=p, training=training)
