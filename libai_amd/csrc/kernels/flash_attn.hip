@@ -26,7 +26,25 @@
 //   dK = dS^T Q;   dQ = dS K
 // bwd_kv computes dK,dV (grid over kv tiles); bwd_q computes dQ (grid over
 // q tiles); both recompute S on the fly.
+//
+// Tile classes.  All three kernels sort each 32-row sub-tile, once and with a
+// wave-uniform scalar condition (the wave's base row goes through
+// readfirstlane), into
+//   interior: every (q, kv) pair visible -- all q rows < Sq, all kv rows <
+//             sk_eff, under `causal` lowest q >= highest kv, under WINDOW the
+//             farthest pair inside the band;
+//   edge:     everything else (diagonal, ragged, padded, band border).
+// One generic lambda per kernel, instantiated on `MASKED`, gives both bodies.
+// The interior body has no validity compares, selects or sentinel guards; the
+// edge body keeps sentinel scores and exact zeros for masked P and dS, by
+// selects / bitwise AND masks, never by per-element exec branches.  Visible
+// entries are computed expression for expression alike in both, so the class
+// of a tile never changes a result bit.  Accumulators and MFMAs stay outside
+// the class branch: only the element values merge after it (accumulators
+// merged through the branch cost 400-600 B/lane of scratch).
 #include "common.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -40,9 +58,8 @@ typedef float f32x16_t __attribute__((ext_vector_type(16)));
 #define QBLK (QB * NW)
 #define KVB 64   // kv rows per LDS tile (forward)
 
-// A/B experiment knobs (guide T5: s_setprio around MFMA clusters, +4-7% on
-// attention when wave roles diverge; FLASH_STAGGER decorrelates the waves'
-// subtile order so they don't hit the same stall points in lockstep).
+// A/B experiment knob (guide T5: s_setprio around MFMA clusters; measured
+// slower on these lockstep 4-wave blocks, profiles/pmc_flash_attention.md).
 #ifdef FLASH_SETPRIO
 #define PRIO_HI() __builtin_amdgcn_s_setprio(1)
 #define PRIO_LO() __builtin_amdgcn_s_setprio(0)
@@ -62,6 +79,24 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
   r.h[0] = (bf16_t)lo;
   r.h[1] = (bf16_t)hi;
   return r.u;
+}
+
+// Edge-tile masking: x where the mask is all ones, an exact +0 where it is 0.
+// A bitwise AND instead of `valid ? x : 0` keeps the backend from turning the
+// select of an expensive operand (exp, LDS read) back into a per-element
+// divergent branch, and also discards an inf/NaN of a masked entry.
+__device__ __forceinline__ float and_f32(float x, uint32_t m) {
+  return __uint_as_float(__float_as_uint(x) & m);
+}
+
+// Contraction is pinned by hand where the backward kernels form dS, so that
+// every instantiation and both tile-class bodies round alike, whatever the
+// compiler would pick per body: bwd_kv rounds the product dPd * keep before
+// subtracting Drow, bwd_q fuses it (explicit fmaf at its call site) -- each as
+// its single body always compiled.
+__device__ __forceinline__ float mul_then_sub(float a, float b, float c) {
+#pragma clang fp contract(off)
+  return a * b - c;
 }
 
 // D-layout regs (8 consecutive: rows {0..3}+4hi and {8..11}+4hi of a 16-row
@@ -222,7 +257,9 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
   const int bh = blockIdx.y;
   const int b = bh / H, h = bh % H;
   const int q_block = blockIdx.x * QBLK;
-  const int q_base = q_block + wave * QB;
+  // wave-uniform by construction; readfirstlane tells the compiler, so the
+  // sub-tile skips and the tile-class test become scalar branches
+  const int q_base = __builtin_amdgcn_readfirstlane(q_block + wave * QB);
 
   const int hk = h / kv_group;  // GQA: query head -> its kv head
   const bf16_t* qp = q + b * q_sb + h * q_sh;
@@ -296,47 +333,68 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
 
     // scores are already in the exp2 domain (Q pre-scale); m/l run in it too
     float sv[2][16];
-    float pmax = -3.0e38f;
-    // kv - q of this lane's first score; the per-register offsets below are
-    // compile-time constants (exact in fp32)
-    float rel0 = 0.f;
-    if constexpr (ALIBI) rel0 = (float)(kv0 + 4 * hi - qg);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int kva = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-      int kvb = kva + 32;
-      float a = s0[r], bb = s1[r];
-      if constexpr (ALIBI) {  // before the masks: masked entries keep the sentinel
-        const float off = (float)((r & 3) + 8 * (r >> 2));
-        a = fmaf(slope2, rel0 + off, a);
-        bb = fmaf(slope2, rel0 + (off + 32.f), bb);
-      }
-      if (kva >= sk_eff || (causal && kva > qg)) a = -3.0e38f;
-      if (kvb >= sk_eff || (causal && kvb > qg)) bb = -3.0e38f;
-      if constexpr (WINDOW) {
-        if (qg - kva >= window) a = -3.0e38f;
-        if (qg - kvb >= window) bb = -3.0e38f;
-      }
-      sv[0][r] = a;
-      sv[1][r] = bb;
-      pmax = fmaxf(pmax, fmaxf(a, bb));
-    }
-    pmax = fmaxf(pmax, __shfl_xor(pmax, 32));
-
-    const float m_new = fmaxf(m_run, pmax);
-    const float alpha = (m_run <= -3.0e38f) ? 0.f : __builtin_amdgcn_exp2f(m_run - m_new);
-    m_run = m_new;
-    float lsum = 0.f;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
+    // Tile class (wave-uniform, scalar branch): an interior sub-tile has every
+    // (q, kv) pair visible -- all keys < sk_eff, all rows < Sq, under causal
+    // its lowest q >= its highest kv, under WINDOW its farthest pair inside
+    // the band -- and runs the body without compares, selects or sentinels.
+    bool interior = kv0 + KVB <= sk_eff && q_base + QB <= Sq &&
+                    (!causal || q_base >= kv0 + KVB - 1);
+    if constexpr (WINDOW) interior = interior && (q_base + QB - 1 - kv0 < window);
+    auto softmax_tile = [&](auto masked_c) {
+      constexpr bool MASKED = decltype(masked_c)::value;
+      float pmax = -3.0e38f;
+      // kv - q of this lane's first score; the per-register offsets below are
+      // compile-time constants (exact in fp32)
+      float rel0 = 0.f;
+      if constexpr (ALIBI) rel0 = (float)(kv0 + 4 * hi - qg);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        float e = (sv[t][r] <= -3.0e38f) ? 0.f : __builtin_amdgcn_exp2f(sv[t][r] - m_new);
-        sv[t][r] = e;
-        lsum += e;
+        int kva = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        int kvb = kva + 32;
+        float a = s0[r], bb = s1[r];
+        if constexpr (ALIBI) {  // before the masks: masked entries keep the sentinel
+          const float off = (float)((r & 3) + 8 * (r >> 2));
+          a = fmaf(slope2, rel0 + off, a);
+          bb = fmaf(slope2, rel0 + (off + 32.f), bb);
+        }
+        if constexpr (MASKED) {
+          if (kva >= sk_eff || (causal && kva > qg)) a = -3.0e38f;
+          if (kvb >= sk_eff || (causal && kvb > qg)) bb = -3.0e38f;
+          if constexpr (WINDOW) {
+            if (qg - kva >= window) a = -3.0e38f;
+            if (qg - kvb >= window) bb = -3.0e38f;
+          }
+        }
+        sv[0][r] = a;
+        sv[1][r] = bb;
+        pmax = fmaxf(pmax, fmaxf(a, bb));
       }
-    lsum += __shfl_xor(lsum, 32);
-    l_run = l_run * alpha + lsum;
+      pmax = fmaxf(pmax, __shfl_xor(pmax, 32));
+
+      const float m_new = fmaxf(m_run, pmax);
+      // interior: m_new is finite, so a first-tile m_run of -3.0e38 gives
+      // exp2(-3.0e38) = 0 without the guard, and every score is finite
+      float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+      if constexpr (MASKED) alpha = (m_run <= -3.0e38f) ? 0.f : alpha;
+      m_run = m_new;
+      float lsum = 0.f;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float e = __builtin_amdgcn_exp2f(sv[t][r] - m_new);
+          if constexpr (MASKED) e = (sv[t][r] <= -3.0e38f) ? 0.f : e;
+          sv[t][r] = e;
+          lsum += e;
+        }
+      lsum += __shfl_xor(lsum, 32);
+      l_run = l_run * alpha + lsum;
+      return alpha;
+    };
+    // the accumulators stay out of the two-way branch (only sv, m, l and
+    // alpha merge after it)
+    const float alpha = interior ? softmax_tile(std::false_type{})
+                                 : softmax_tile(std::true_type{});
 #pragma unroll
     for (int t = 0; t < DT; ++t)
 #pragma unroll
@@ -430,27 +488,14 @@ __global__ void rowdot_kernel(const bf16_t* __restrict__ dout,
 // ===========================================================================
 // backward over kv tiles: dK, dV   (block = 128 kv rows, wave owns 32)
 // ===========================================================================
-// FLASH_BWD_DBUF: double-buffered q/do staging (2-phase pipeline) at
-// 2 blocks/CU — next tile's global loads fly during this tile's compute,
-// one barrier per tile instead of two.
-#ifdef FLASH_BWD_DBUF
-#define BWD_KV_NBUF 2
-#define BWD_KV_OCC 2
-#else
-#define BWD_KV_NBUF 1
-#define BWD_KV_OCC 3
-#endif
-// The D=64 ALiBi instantiation targets 2 waves/SIMD: at 3 (168 VGPRs) the
-// extra term pushes the staging-address spills from 64 to 72 B/lane, at 2 it
-// takes 202 VGPRs with no scratch and measured faster on MI355X (b4 s1024 h16
-// fwd+bwd 293 us vs 333 us, profiles/alibi_flash.md).  The non-ALiBi
-// instantiation keeps its target.
-// The D=64 sliding-window instantiation targets 2 waves/SIMD for the same
-// reason: at 3 its extra compares raise the scratch to 76 B/lane, above the
-// 64 B of the plain build; at 2 it takes 204 VGPRs with no scratch.
+// Every instantiation targets 2 waves/SIMD.  At D=64 that leaves room to hold
+// the lane's K and V row fragments in registers (32 VGPRs), so the S/dPd
+// chain has no operand fetch left in it: 188 VGPRs, no scratch.  The 3-wave
+// form of the plain instantiation (159 VGPRs, no scratch, K/V re-read from L2
+// per sub-tile) measured 2 % slower end to end (profiles/flash_tile_classes.md).
+// D=128 (128 accumulator VGPRs) re-reads K/V per use and sits at 244-256.
 template <int D, bool ALIBI, bool WINDOW>
-__global__ __launch_bounds__(256, D == 64 ? ((ALIBI || WINDOW) ? 2 : BWD_KV_OCC)
-                                          : 2) void flash_bwd_kv_kernel(
+__global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ drow,
@@ -464,18 +509,18 @@ __global__ __launch_bounds__(256, D == 64 ? ((ALIBI || WINDOW) ? 2 : BWD_KV_OCC)
     int window) {
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
-  // D=64: 64-row staging tiles + persistent K/V fragments.  D=128: 32-row
-  // tiles and K/V fragments re-read from global per use (L2-resident) --
-  // the persistent variant spills 78 VGPRs.
+  // D=64: 64-row staging tiles.  D=128: 32-row tiles.
   constexpr int QTILE = (D == 64) ? 2 * QB : QB;
   constexpr int NSUB = QTILE / QB;
 
-  __shared__ __align__(16) bf16_t q_row[BWD_KV_NBUF][QTILE * D];
-  __shared__ __align__(16) bf16_t q_tr[BWD_KV_NBUF][QTILE * D];
-  __shared__ __align__(16) bf16_t do_row[BWD_KV_NBUF][QTILE * D];
-  __shared__ __align__(16) bf16_t do_tr[BWD_KV_NBUF][QTILE * D];
-  __shared__ float lse_lds[BWD_KV_NBUF][QTILE];
-  __shared__ float drow_lds[BWD_KV_NBUF][QTILE];
+  __shared__ __align__(16) bf16_t q_row[QTILE * D];
+  __shared__ __align__(16) bf16_t q_tr[QTILE * D];
+  __shared__ __align__(16) bf16_t do_row[QTILE * D];
+  __shared__ __align__(16) bf16_t do_tr[QTILE * D];
+  // row constants, 16B-aligned: a D-layout register run covers 4 consecutive
+  // q rows, so each run takes its lse/Drow with one unconditional ds_read_b128
+  __shared__ __align__(16) float lse_lds[QTILE];
+  __shared__ __align__(16) float drow_lds[QTILE];
 
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -489,23 +534,39 @@ __global__ __launch_bounds__(256, D == 64 ? ((ALIBI || WINDOW) ? 2 : BWD_KV_OCC)
   const int bhk = blockIdx.y;
   const int b = bhk / Hkv, hk = bhk % Hkv;
   const int kv_block = blockIdx.x * QBLK;   // 128 kv rows per block
-  const int kv_base = kv_block + wave * QB; // this wave's 32 kv rows
+  // this wave's 32 kv rows; wave-uniform (scalar skips and tile-class branch)
+  const int kv_base = __builtin_amdgcn_readfirstlane(kv_block + wave * QB);
   const int kvg = kv_base + l31;            // lane's kv row
 
   const bf16_t* kp = k + b * k_sb + hk * k_sh;
   const bf16_t* vp = v + b * v_sb + hk * v_sh;
 
-  // per-lane K and V row fragments (B-operands: lane j = kv).  Persistent in
-  // registers for D=64; re-read from global (L2) per use for D=128.
-  // K/V row fragments are re-read from global per use (L2-resident: one K row
-  // per lane, reused across every q tile).  Keeping them persistent cost 32
-  // VGPRs and held the kernel at 2 waves/SIMD.
+  // per-lane K and V row fragments (B-operands: lane j = kv), loop-invariant.
+  // D=64 holds them in registers; D=128 re-reads them from global per use
+  // (L2-resident: one K row per lane; register budget, see above).
+  constexpr bool KV_PERSIST = D == 64;
   const int kvr_ld = min(kvg, Sk - 1);
-  auto get_kf = [&](int c) {
+  auto load_kf = [&](int c) {
     return *(const bf16x8_t*)(kp + (int64_t)kvr_ld * k_ss + c * 16 + hi * 8);
   };
-  auto get_vf = [&](int c) {
+  auto load_vf = [&](int c) {
     return *(const bf16x8_t*)(vp + (int64_t)kvr_ld * v_ss + c * 16 + hi * 8);
+  };
+  bf16x8_t kf[KV_PERSIST ? KC : 1], vf[KV_PERSIST ? KC : 1];
+  if constexpr (KV_PERSIST) {
+#pragma unroll
+    for (int c = 0; c < KC; ++c) {
+      kf[c] = load_kf(c);
+      vf[c] = load_vf(c);
+    }
+  }
+  auto get_kf = [&](int c) {
+    if constexpr (KV_PERSIST) return kf[c];
+    else return load_kf(c);
+  };
+  auto get_vf = [&](int c) {
+    if constexpr (KV_PERSIST) return vf[c];
+    else return load_vf(c);
   };
 
   f32x16_t dk_acc[DT], dv_acc[DT];
@@ -529,42 +590,49 @@ __global__ __launch_bounds__(256, D == 64 ? ((ALIBI || WINDOW) ? 2 : BWD_KV_OCC)
   if constexpr (WINDOW) q_hi = min(Sq, kv_block + QBLK + window - 1);
   const int n_qtiles = (kv_block < sk_eff) ? CDIV(q_hi, QTILE) : 0;
 
+  // Dropout key of element (q, kv4), first mixer word, mod 2^32:
+  //   (q * Sk4 + kv4) * LO_MUL = q_run * sk4_mul + hkey_lane
+  // with q = q_run + 4 * hi + (l31 & 3).  q_run is wave-uniform, so each run
+  // costs one scalar multiply and one add on a single loop-invariant VGPR
+  // (written as in drop_hash4 the compiler keeps one pre-multiplied VGPR base
+  // per run of the unrolled tile: 8 registers, spilled).
+  const uint32_t sk4_mul = (uint32_t)(Sk >> 2) * RND_HASH_LO_MUL;
+  const uint32_t hkey_lane =
+      (uint32_t)(4 * hi + (l31 & 3)) * sk4_mul +
+      (uint32_t)((kv_base + (l31 & ~3)) >> 2) * RND_HASH_LO_MUL;
+
   for (int g = 0; g < kv_group; ++g) {
   const int h = hk * kv_group + g;
   const int bh = b * H + h;  // q-head index: lse/drow rows + dropout key
+  const uint32_t hkey_head = (uint32_t)seed ^ ((uint32_t)bh * RND_HASH_HI_MUL) ^
+                             (uint32_t)(seed >> 32);
   const bf16_t* qp = q + b * q_sb + h * q_sh;
   const bf16_t* dop = dout + b * do_sb + h * do_sh;
   // ALiBi slope of THIS query head (the grid spans kv heads)
   float slope = 0.f;
   if constexpr (ALIBI) slope = alibi_slopes[h];
 
-  auto stage_all = [&](int buf, int qt) {
+  auto stage_all = [&](int qt) {
     const int q0 = qt * QTILE;
-    stage_tile<QTILE, D, true, true>(q_row[buf], q_tr[buf], qp, q0, Sq, q_ss, tid);
-    stage_tile<QTILE, D, true, true>(do_row[buf], do_tr[buf], dop, q0, Sq, do_ss,
-                                     tid);
+    stage_tile<QTILE, D, true, true>(q_row, q_tr, qp, q0, Sq, q_ss, tid);
+    stage_tile<QTILE, D, true, true>(do_row, do_tr, dop, q0, Sq, do_ss, tid);
     if (tid < QTILE) {
-      int qr = min(q0 + tid, Sq - 1);
-      lse_lds[buf][tid] = lse[(int64_t)bh * Sq + qr];
-      drow_lds[buf][tid] = drow[(int64_t)bh * Sq + qr];
+      int qr = min(q0 + tid, Sq - 1);  // clamped: every staged row is readable
+      lse_lds[tid] = lse[(int64_t)bh * Sq + qr];
+      drow_lds[tid] = drow[(int64_t)bh * Sq + qr];
     }
   };
 
-  auto compute_tile = [&](int buf, int q0) {
+  auto compute_tile = [&](int q0) {
     if (causal && q0 + QTILE - 1 < kv_base) return;  // entirely above diag
     if constexpr (WINDOW) {  // entirely below this wave's band
       if (q0 - (kv_base + QB - 1) >= window) return;
     }
 
-#pragma unroll
-    for (int sub_i = 0; sub_i < NSUB; ++sub_i) {
-#ifdef FLASH_STAGGER
-      // per-wave subtile order: decorrelates the waves' stall points
-      // (subtiles are independent; accumulation order is irrelevant)
-      const int sub = (sub_i + wave) % NSUB;
-#else
-      const int sub = sub_i;
-#endif
+    // rolled: one copy of the four element bodies, and no per-sub-tile set of
+    // hoisted addresses (unrolled, D=64 took 254 VGPRs instead of 188)
+#pragma unroll 1
+    for (int sub = 0; sub < NSUB; ++sub) {
       const int q0s = q0 + sub * QB;
       if (causal && q0s + QB - 1 < kv_base) continue;
       if constexpr (WINDOW) {
@@ -578,19 +646,30 @@ __global__ __launch_bounds__(256, D == 64 ? ((ALIBI || WINDOW) ? 2 : BWD_KV_OCC)
       PRIO_HI();
 #pragma unroll
       for (int c = 0; c < KC; ++c) {
-        bf16x8_t qa = row_img_frag<D>(q_row[buf], ro + l31, c, hi);
+        bf16x8_t qa = row_img_frag<D>(q_row, ro + l31, c, hi);
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, get_kf(c), s, 0, 0, 0);
-        bf16x8_t da = row_img_frag<D>(do_row[buf], ro + l31, c, hi);
+        bf16x8_t da = row_img_frag<D>(do_row, ro + l31, c, hi);
         dpd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, get_vf(c), dpd, 0, 0, 0);
       }
       PRIO_LO();
 
-      // per-chunk: compute Pd/dS for 8 regs, repack, feed the MFMAs — the
-      // short lifetimes keep the kernel at 3 waves/SIMD (full pd[16]/ds[16]
-      // arrays held it at 2).
+      // tile class, as in the forward (wave-uniform, scalar branch; the
+      // ds_read_b64_tr_b16 reads below need EXEC all ones)
+      bool interior = q0s + QB <= Sq && kv_base + QB <= sk_eff &&
+                      (!causal || q0s >= kv_base + QB - 1);
+      if constexpr (WINDOW)
+        interior = interior && (q0s + QB - 1 - kv_base < window);
+
+      // per-chunk: compute Pd/dS for 8 regs, repack, feed the MFMAs (short
+      // lifetimes).  The element body is instantiated on MASKED (tile class)
+      // and on DROP, so that no uniform branch on p_drop splits a body; only
+      // pd8/ds8 merge after the branch, the accumulators never enter it.
 #pragma unroll
       for (int c16 = 0; c16 < 2; ++c16) {
         float pd8[8], ds8[8];
+        auto elems = [&](auto masked_c, auto drop_c) {
+        constexpr bool MASKED = decltype(masked_c)::value;
+        constexpr bool DROP = decltype(drop_c)::value;
         // dropout hashes, quad-distributed: each element needs the draw for
         // (its qrow, lane's kv4); the 4 lanes of a quad share kv4 and the 4
         // qrows of a run are consecutive, so lane (l&3) computes the run's
@@ -598,14 +677,24 @@ __global__ __launch_bounds__(256, D == 64 ? ((ALIBI || WINDOW) ? 2 : BWD_KV_OCC)
         // (A straight per-element hash makes the compiler hoist 16 hash
         // bases per subtile -> 25+ VGPR spills into the hot loop.)
         const uint32_t thr8 = drop_threshold_u8(p_drop);
-        const int kv4q = (kv_base + (l31 & ~3)) >> 2;
         const int byte_sh = (l31 & 3) * 8;
 #pragma unroll
         for (int r4 = 0; r4 < 2; ++r4) {
           const int qbase = q0s + c16 * 16 + 8 * r4 + 4 * hi;
+          // the run's four row constants, one unconditional 16B read each
+          const float4 lse4 = *(const float4*)__builtin_assume_aligned(
+              &lse_lds[qbase - q0], 16);
+          const float4 drow4 = *(const float4*)__builtin_assume_aligned(
+              &drow_lds[qbase - q0], 16);
+          const float lse_r[4] = {lse4.x, lse4.y, lse4.z, lse4.w};
+          const float drow_r[4] = {drow4.x, drow4.y, drow4.z, drow4.w};
           uint32_t hq = 0;
-          if (p_drop > 0.f)
-            hq = drop_hash4(seed, bh, Sq, Sk >> 2, qbase + (l31 & 3), kv4q);
+          if constexpr (DROP)  // == drop_hash4(.., qbase + (l31 & 3), kv4q)
+            hq = rnd_hash_mix(
+                hkey_head ^
+                (__builtin_amdgcn_readfirstlane(
+                     (uint32_t)(q0s + c16 * 16 + 8 * r4) * sk4_mul) +
+                 hkey_lane));
           uint32_t hqj[4];
           hqj[0] = (uint32_t)__builtin_amdgcn_mov_dpp((int)hq, 0x00, 0xF, 0xF, true);
           hqj[1] = (uint32_t)__builtin_amdgcn_mov_dpp((int)hq, 0x55, 0xF, 0xF, true);
@@ -616,23 +705,41 @@ __global__ __launch_bounds__(256, D == 64 ? ((ALIBI || WINDOW) ? 2 : BWD_KV_OCC)
             const int k = r4 * 4 + j;
             const int r = c16 * 8 + k;
             const int qrow = qbase + j;
-            bool valid =
-                qrow < Sq && kvg < sk_eff && (!causal || qrow >= kvg);
-            if constexpr (WINDOW) valid = valid && (qrow - kvg < window);
-            float p = 0.f;
-            float sc = s[r] * scale;
-            // (kv - q) is recomputed per element: nothing extra stays live
-            // across the subtile on this kernel's register budget
-            if constexpr (ALIBI) sc = fmaf(slope, (float)(kvg - qrow), sc);
-            if (valid) p = __expf(sc - lse_lds[buf][qrow - q0]);
-            float keep = valid ? 1.f : 0.f;
-            if (p_drop > 0.f && valid)
+            // x = scale * s (+ bias) - lse, the exp argument.  (kv - q) is
+            // recomputed per element: nothing extra stays live across the
+            // subtile on this kernel's register budget
+            float x;
+            if constexpr (ALIBI)
+              x = fmaf(slope, (float)(kvg - qrow), s[r] * scale) - lse_r[j];
+            else
+              x = fmaf(s[r], scale, -lse_r[j]);
+            float keep = 1.f;
+            if constexpr (DROP)
               keep = (((hqj[j] >> byte_sh) & 0xFFu) >= thr8) ? ks : 0.f;
-            pd8[k] = p * keep;
-            ds8[k] = valid
-                         ? scale * p * (dpd[r] * keep - drow_lds[buf][qrow - q0])
-                         : 0.f;
+            if constexpr (MASKED) {
+              // select-based: masked P and dS are exact zeros
+              bool valid =
+                  qrow < Sq && kvg < sk_eff && (!causal || qrow >= kvg);
+              if constexpr (WINDOW) valid = valid && (qrow - kvg < window);
+              const uint32_t vm = valid ? 0xFFFFFFFFu : 0u;
+              const float p = and_f32(__expf(x), vm);
+              pd8[k] = p * keep;
+              ds8[k] = and_f32(
+                  scale * p * mul_then_sub(dpd[r], keep, drow_r[j]), vm);
+            } else {
+              const float p = __expf(x);
+              pd8[k] = p * keep;
+              ds8[k] = scale * p * mul_then_sub(dpd[r], keep, drow_r[j]);
+            }
           }
+        }
+        };  // elems
+        if (p_drop > 0.f) {
+          if (interior) elems(std::false_type{}, std::true_type{});
+          else elems(std::true_type{}, std::true_type{});
+        } else {
+          if (interior) elems(std::false_type{}, std::false_type{});
+          else elems(std::true_type{}, std::false_type{});
         }
         bf16x8_t pdf = repack_chunk(pd8);
         bf16x8_t dsf = repack_chunk(ds8);
@@ -640,10 +747,10 @@ __global__ __launch_bounds__(256, D == 64 ? ((ALIBI || WINDOW) ? 2 : BWD_KV_OCC)
         PRIO_HI();
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
-          bf16x8_t dof = tr_img_frag<D>(do_tr[buf], qc, dt, lane);
+          bf16x8_t dof = tr_img_frag<D>(do_tr, qc, dt, lane);
           dv_acc[dt] =
               __builtin_amdgcn_mfma_f32_32x32x16_bf16(dof, pdf, dv_acc[dt], 0, 0, 0);
-          bf16x8_t qtf = tr_img_frag<D>(q_tr[buf], qc, dt, lane);
+          bf16x8_t qtf = tr_img_frag<D>(q_tr, qc, dt, lane);
           dk_acc[dt] =
               __builtin_amdgcn_mfma_f32_32x32x16_bf16(qtf, dsf, dk_acc[dt], 0, 0, 0);
         }
@@ -652,30 +759,12 @@ __global__ __launch_bounds__(256, D == 64 ? ((ALIBI || WINDOW) ? 2 : BWD_KV_OCC)
     }
   };  // compute_tile
 
-#ifdef FLASH_BWD_DBUF
-  {
-    int cur = 0;
-    if (qt_start < n_qtiles) {
-      __syncthreads();  // previous g's reads complete before re-staging
-      stage_all(0, qt_start);
-      __syncthreads();
-    }
-    for (int qt = qt_start; qt < n_qtiles; ++qt) {
-      if (qt + 1 < n_qtiles)
-        stage_all(cur ^ 1, qt + 1);  // next tile's loads fly under compute
-      compute_tile(cur, qt * QTILE);
-      __syncthreads();
-      cur ^= 1;
-    }
-  }
-#else
   for (int qt = qt_start; qt < n_qtiles; ++qt) {
     __syncthreads();
-    stage_all(0, qt);
+    stage_all(qt);
     __syncthreads();
-    compute_tile(0, qt * QTILE);
+    compute_tile(qt * QTILE);
   }
-#endif
 
   }  // group loop (GQA)
 
@@ -732,7 +821,8 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
   const int bh = blockIdx.y;
   const int b = bh / H, h = bh % H;
   const int q_block = blockIdx.x * QBLK;
-  const int q_base = q_block + wave * QB;
+  // wave-uniform: scalar sub-tile skips and tile-class branch (see forward)
+  const int q_base = __builtin_amdgcn_readfirstlane(q_block + wave * QB);
   const int qg = q_base + l31;
 
   const int hk = h / kv_group;  // GQA
@@ -741,25 +831,18 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
   const bf16_t* vp = v + b * v_sb + hk * v_sh;
   const bf16_t* dop = dout + b * do_sb + h * do_sh;
 
-  // per-lane Q and dO row fragments (B-operands: lane j = q); persistent for
-  // D=64, re-read from global (L2) per use for D=128 (register budget).
+  // per-lane Q and dO row fragments (B-operands: lane j = q), loop-invariant
+  // and held in registers at both head dims.  At D=128 that is 64 VGPRs and
+  // 2 waves/SIMD (223-249 VGPRs, no scratch): re-reading them from global in
+  // front of each MFMA of the S/dPd chain measured 2-3x slower, at 2 waves
+  // and at 3 (profiles/flash_tile_classes.md).
   const int qr_ld = min(qg, Sq - 1);
-  bf16x8_t qf[D == 64 ? KC : 1], dof[D == 64 ? KC : 1];
-  if constexpr (D == 64) {
+  bf16x8_t qf[KC], dof[KC];
 #pragma unroll
-    for (int c = 0; c < KC; ++c) {
-      qf[c] = *(const bf16x8_t*)(qp + (int64_t)qr_ld * q_ss + c * 16 + hi * 8);
-      dof[c] = *(const bf16x8_t*)(dop + (int64_t)qr_ld * do_ss + c * 16 + hi * 8);
-    }
+  for (int c = 0; c < KC; ++c) {
+    qf[c] = *(const bf16x8_t*)(qp + (int64_t)qr_ld * q_ss + c * 16 + hi * 8);
+    dof[c] = *(const bf16x8_t*)(dop + (int64_t)qr_ld * do_ss + c * 16 + hi * 8);
   }
-  auto get_qf = [&](int c) {
-    if constexpr (D == 64) return qf[c];
-    else return *(const bf16x8_t*)(qp + (int64_t)qr_ld * q_ss + c * 16 + hi * 8);
-  };
-  auto get_dof = [&](int c) {
-    if constexpr (D == 64) return dof[c];
-    else return *(const bf16x8_t*)(dop + (int64_t)qr_ld * do_ss + c * 16 + hi * 8);
-  };
   const float lse_lane = lse[(int64_t)bh * Sq + min(qg, Sq - 1)];
   const float drow_lane = drow[(int64_t)bh * Sq + min(qg, Sq - 1)];
   float slope = 0.f;
@@ -803,37 +886,56 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
 #pragma unroll
       for (int c = 0; c < KC; ++c) {
         bf16x8_t ka = row_img_frag<D>(k_row, ro + l31, c, hi);
-        st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, get_qf(c), st, 0, 0, 0);
+        st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qf[c], st, 0, 0, 0);
         bf16x8_t va = row_img_frag<D>(v_row, ro + l31, c, hi);
-        dpdt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, get_dof(c), dpdt, 0, 0, 0);
+        dpdt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, dof[c], dpdt, 0, 0, 0);
       }
       PRIO_LO();
 
       float ds[16];
-      const uint32_t thr8 = drop_threshold_u8(p_drop);
-      // kv - q of this lane's first score (ALiBi)
-      float rel0 = 0.f;
-      if constexpr (ALIBI) rel0 = (float)(kv0s + 4 * hi - qg);
+      // tile class, as in the forward (wave-uniform, scalar branch)
+      bool interior = kv0s + QB <= sk_eff && q_base + QB <= Sq &&
+                      (!causal || q_base >= kv0s + QB - 1);
+      if constexpr (WINDOW)
+        interior = interior && (q_base + QB - 1 - kv0s < window);
+      auto ds_tile = [&](auto masked_c) {
+        constexpr bool MASKED = decltype(masked_c)::value;
+        const uint32_t thr8 = drop_threshold_u8(p_drop);
+        // kv - q of this lane's first score (ALiBi)
+        float rel0 = 0.f;
+        if constexpr (ALIBI) rel0 = (float)(kv0s + 4 * hi - qg);
 #pragma unroll
-      for (int r4 = 0; r4 < 4; ++r4) {
-        const int kvb = kv0s + 8 * r4 + 4 * hi;  // 4-aligned kv run
-        const uint32_t h = (p_drop > 0.f)
-                               ? drop_hash4(seed, bh, Sq, Sk >> 2, qg, kvb >> 2)
-                               : 0;
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const int kvb = kv0s + 8 * r4 + 4 * hi;  // 4-aligned kv run
+          const uint32_t h = (p_drop > 0.f)
+                                 ? drop_hash4(seed, bh, Sq, Sk >> 2, qg, kvb >> 2)
+                                 : 0;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int r = r4 * 4 + j;
-          const int kv = kvb + j;
-          bool valid = kv < sk_eff && qg < Sq && (!causal || kv <= qg);
-          if constexpr (WINDOW) valid = valid && (qg - kv < window);
-          float sc = st[r] * scale;
-          if constexpr (ALIBI) sc = fmaf(slope, rel0 + (float)(8 * r4 + j), sc);
-          float p = valid ? __expf(sc - lse_lane) : 0.f;
-          float keep = (p_drop > 0.f && valid) ? drop_keep_byte(h, j, thr8, ks)
-                                               : (valid ? 1.f : 0.f);
-          ds[r] = valid ? scale * p * (dpdt[r] * keep - drow_lane) : 0.f;
+          for (int j = 0; j < 4; ++j) {
+            const int r = r4 * 4 + j;
+            const int kv = kvb + j;
+            float x;  // scale * s (+ bias) - lse, the exp argument
+            if constexpr (ALIBI)
+              x = fmaf(slope, rel0 + (float)(8 * r4 + j), st[r] * scale) - lse_lane;
+            else
+              x = fmaf(st[r], scale, -lse_lane);
+            if constexpr (MASKED) {
+              bool valid = kv < sk_eff && qg < Sq && (!causal || kv <= qg);
+              if constexpr (WINDOW) valid = valid && (qg - kv < window);
+              const uint32_t vm = valid ? 0xFFFFFFFFu : 0u;
+              float p = and_f32(__expf(x), vm);
+              float keep = (p_drop > 0.f) ? drop_keep_byte(h, j, thr8, ks) : 1.f;
+              ds[r] = and_f32(scale * p * fmaf(dpdt[r], keep, -drow_lane), vm);
+            } else {
+              float p = __expf(x);
+              float keep = (p_drop > 0.f) ? drop_keep_byte(h, j, thr8, ks) : 1.f;
+              ds[r] = scale * p * fmaf(dpdt[r], keep, -drow_lane);
+            }
+          }
         }
-      }
+      };
+      if (interior) ds_tile(std::false_type{});
+      else ds_tile(std::true_type{});
 
       // dQ^T[d][q] += K^T x dS^T
       PRIO_HI();
