@@ -103,7 +103,7 @@ void flash_fwd_bf16(const void*, const void*, const void*, void*, float*,
                     const int*, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int, int, int, int, int, float, float, uint64_t, int, int,
-                    const float*, int, hipStream_t);
+                    const float*, int, const float*, hipStream_t);
 void flash_bwd_bf16(const void*, const void*, const void*, const void*, const void*,
                     const float*, float*, const int*, void*, void*, void*, int64_t,
                     int64_t,
@@ -111,7 +111,7 @@ void flash_bwd_bf16(const void*, const void*, const void*, const void*, const vo
                     int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int64_t, int, int, int, int, int, float, float, uint64_t, int,
-                    int, const float*, int, hipStream_t);
+                    int, const float*, int, const float*, float*, hipStream_t);
 void attn_dropout_apply_bf16(void*, int64_t, int64_t, int64_t, float, uint64_t,
                              hipStream_t);
 void attn_dropout_apply_f32(void*, int64_t, int64_t, int64_t, float, uint64_t,
@@ -452,6 +452,24 @@ static int window_arg(int64_t window, bool causal, bool has_alibi, int64_t Sk,
   return (int)std::min<int64_t>(window, std::max<int64_t>(Sk, 1));
 }
 
+// optional relative-position table (T5): fp32 [H, Sq + Sk - 1], one row per
+// QUERY head, entry kv - q + Sq - 1.  Not combinable with ALiBi or a window.
+static const float* rel_bias_ptr(const c10::optional<torch::Tensor>& table,
+                                 const torch::Tensor& q, int64_t H, int64_t Sq,
+                                 int64_t Sk, bool has_alibi, int64_t window,
+                                 const char* op) {
+  if (!table.has_value()) return nullptr;
+  TORCH_CHECK(!has_alibi, op, ": rel_bias cannot be combined with alibi_slopes");
+  TORCH_CHECK(window == 0, op, ": rel_bias cannot be combined with a sliding window");
+  TORCH_CHECK(table->scalar_type() == torch::kFloat32 && table->is_cuda() &&
+                  table->get_device() == q.get_device() && table->is_contiguous() &&
+                  table->dim() == 2 && table->size(0) == H &&
+                  table->size(1) == Sq + Sk - 1,
+              op, ": rel_bias must be a contiguous fp32 tensor of shape "
+              "[H, Sq + Sk - 1] (query heads) on q's device");
+  return table->data_ptr<float>();
+}
+
 // ---------------------------------------------------------------------------
 // fused single-query decode attention (K16 serving path)
 // ---------------------------------------------------------------------------
@@ -558,7 +576,8 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
                                                    bool causal,
                                                    c10::optional<torch::Tensor> kv_len,
                                                    c10::optional<torch::Tensor> alibi_slopes,
-                                                   int64_t window) {
+                                                   int64_t window,
+                                                   c10::optional<torch::Tensor> rel_bias) {
   const int* kvl = nullptr;
   if (kv_len.has_value()) {
     TORCH_CHECK(kv_len->scalar_type() == torch::kInt32 && kv_len->is_cuda() &&
@@ -582,6 +601,8 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
   const float* slopes = alibi_slopes_ptr(alibi_slopes, q, H);
   const int win = window_arg(window, causal, slopes != nullptr, Sk, "flash_fwd");
   TORCH_CHECK(win == 0 || Sq == Sk, "flash_fwd: a sliding window needs Sq == Sk");
+  const float* relb =
+      rel_bias_ptr(rel_bias, q, H, Sq, Sk, slopes != nullptr, window, "flash_fwd");
   auto o = torch::empty({B, Sq, H, D}, q.options());
   auto lse = torch::empty({B, H, Sq}, q.options().dtype(torch::kFloat32));
   flash_fwd_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
@@ -589,17 +610,20 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
                  k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1),
                  v.stride(2), o.stride(0), o.stride(1), o.stride(2), B, H, Sq, Sk, D,
                  (float)scale, (float)p_drop, (uint64_t)seed, causal ? 1 : 0,
-                 kv_group, slopes, win, cur_stream());
+                 kv_group, slopes, win, relb, cur_stream());
   check_launch("flash_fwd");
   return {o, lse};
 }
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> flash_bwd(
+// Returns (dq, dk, dv), or (dq, dk, dv, d_rel_bias) when a relative-position
+// table is given (fp32, the table's shape, summed over the batch).
+py::tuple flash_bwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o,
     torch::Tensor dout, torch::Tensor lse, double scale, double p_drop, int64_t seed,
     bool causal, c10::optional<torch::Tensor> dqkv,
     c10::optional<torch::Tensor> kv_len,
-    c10::optional<torch::Tensor> alibi_slopes, int64_t window) {
+    c10::optional<torch::Tensor> alibi_slopes, int64_t window,
+    c10::optional<torch::Tensor> rel_bias) {
   const int* kvl = nullptr;
   if (kv_len.has_value()) {
     TORCH_CHECK(kv_len->scalar_type() == torch::kInt32 && kv_len->is_cuda() &&
@@ -614,6 +638,11 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> flash_bwd(
   const float* slopes = alibi_slopes_ptr(alibi_slopes, q, H);
   const int win = window_arg(window, causal, slopes != nullptr, Sk, "flash_bwd");
   TORCH_CHECK(win == 0 || Sq == Sk, "flash_bwd: a sliding window needs Sq == Sk");
+  const float* relb =
+      rel_bias_ptr(rel_bias, q, H, Sq, Sk, slopes != nullptr, window, "flash_bwd");
+  // the dQ kernel accumulates into it with atomics: zero-filled here
+  torch::Tensor d_relb;
+  if (relb != nullptr) d_relb = torch::zeros_like(rel_bias.value());
   TORCH_CHECK(dout.is_contiguous() && o.is_contiguous());
   torch::Tensor dq, dk, dv;
   if (dqkv.has_value()) {
@@ -637,10 +666,11 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> flash_bwd(
       o.stride(2), dout.stride(0), dout.stride(1), dout.stride(2), dq.stride(0),
       dq.stride(1), dq.stride(2), dk.stride(0), dk.stride(1), dk.stride(2),
       dv.stride(0), dv.stride(1), dv.stride(2), B, H, Sq, Sk, D, (float)scale,
-      (float)p_drop, (uint64_t)seed, causal ? 1 : 0, kv_group, slopes, win,
-      cur_stream());
+      (float)p_drop, (uint64_t)seed, causal ? 1 : 0, kv_group, slopes, win, relb,
+      relb != nullptr ? d_relb.data_ptr<float>() : nullptr, cur_stream());
   check_launch("flash_bwd");
-  return {dq, dk, dv};
+  if (relb != nullptr) return py::make_tuple(dq, dk, dv, d_relb);
+  return py::make_tuple(dq, dk, dv);
 }
 
 void attn_dropout_apply(torch::Tensor x, int64_t Sq, int64_t Sk, double p,
@@ -812,11 +842,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embedding_bwd", &embedding_bwd);
   m.def("flash_fwd", &flash_fwd, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("scale"), py::arg("p_drop"), py::arg("seed"), py::arg("causal"),
-        py::arg("kv_len"), py::arg("alibi_slopes") = py::none(), py::arg("window") = 0);
+        py::arg("kv_len"), py::arg("alibi_slopes") = py::none(), py::arg("window") = 0,
+        py::arg("rel_bias") = py::none());
   m.def("flash_bwd", &flash_bwd, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o"), py::arg("dout"), py::arg("lse"), py::arg("scale"),
         py::arg("p_drop"), py::arg("seed"), py::arg("causal"), py::arg("dqkv"),
-        py::arg("kv_len"), py::arg("alibi_slopes") = py::none(), py::arg("window") = 0);
+        py::arg("kv_len"), py::arg("alibi_slopes") = py::none(), py::arg("window") = 0,
+        py::arg("rel_bias") = py::none());
   m.def("attn_dropout_apply", &attn_dropout_apply);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);

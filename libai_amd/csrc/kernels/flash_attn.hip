@@ -231,7 +231,46 @@ __device__ __forceinline__ float drop_keep(uint64_t seed, uint64_t bh, int64_t S
 // included).  Besides the in-register predicate, the kv loops skip every tile
 // that lies entirely below the band, so a q block reads about window + QBLK
 // keys.  The WINDOW=false instantiations never read `window`.
-template <int D, bool ALIBI, bool WINDOW>
+// RELB: compile-time variant for a learned Toeplitz bias (T5 relative
+// positions): rel_bias is fp32 [H, Sq + Sk - 1], one row per QUERY head, and
+// the score of (q, kv) gets rel_bias[h][kv - q + Sq - 1] added in fp32 before
+// the masks.  Each kernel stages the diagonals its current tile can touch
+// into a small LDS table (global index clamped while staging, so the lookups
+// themselves are in range for every lane, padded rows included).  bwd_q also
+// reduces the bias gradient (see there).  The RELB=false instantiations never
+// touch the pointers.
+#define RELB_LOG2E 1.4426950408889634f
+
+// global diagonal index -> staged value; out-of-table diagonals (only padded
+// rows / keys reach them) read a clamped neighbour that is never used
+__device__ __forceinline__ float relb_load(const float* __restrict__ row, int t,
+                                           int n_diag) {
+  return row[min(max(t, 0), n_diag - 1)];
+}
+
+// bwd_q keeps the gradient sums of the diagonals it is working on in an LDS
+// ring: block diagonal a (see the kernel) lives in slot a & (RELB_RING - 1).
+// A kv tile touches fewer than RELB_RING consecutive diagonals, and each one
+// is flushed before the ring wraps onto its slot.
+#define RELB_RING 256
+
+// thread `tid` adds the sum of block diagonal a0 + tid (global diagonal
+// a0 + tid + t_off) to the global gradient and clears the slot.  Diagonals
+// outside the table, and diagonals no visible pair touched, hold an exact
+// zero and issue nothing.
+__device__ __forceinline__ void relb_flush(float* ring, float* __restrict__ grow,
+                                           int tid, int count, int a0, int t_off,
+                                           int n_diag) {
+  if (tid < count) {
+    const int a = a0 + tid;
+    const float g = ring[a & (RELB_RING - 1)];
+    ring[a & (RELB_RING - 1)] = 0.f;
+    const int t = a + t_off;
+    if (g != 0.f && t >= 0 && t < n_diag) atomicAdd(grow + t, g);
+  }
+}
+
+template <int D, bool ALIBI, bool WINDOW, bool RELB>
 __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, bf16_t* __restrict__ o, float* __restrict__ lse,
@@ -239,7 +278,8 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss,
     int64_t v_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh, int H, int Sq, int Sk,
     float scale, float p_drop, uint64_t seed, int causal, int kv_group,
-    const float* __restrict__ alibi_slopes, int window) {
+    const float* __restrict__ alibi_slopes, int window,
+    const float* __restrict__ rel_bias) {
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
 
@@ -247,6 +287,10 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
   // compute (PMC: 43% of forward wave cycles were barrier/wait-parked)
   __shared__ __align__(16) bf16_t k_lds[2 * KVB * D];
   __shared__ __align__(16) bf16_t v_lds[2 * KVB * D];
+  // RELB: the 2*KVB + QBLK - 1 diagonals of one round, times log2e; entry
+  // (kv - kvR) + (QBLK - 1) - (q - q_block)
+  constexpr int FWD_DIAGS = 2 * KVB + QBLK - 1;
+  __shared__ float rb_lds[RELB ? FWD_DIAGS : 1];
 
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -303,12 +347,23 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
   // key any query of this block can see (uniform across the workgroup)
   int round0 = 0;
   if constexpr (WINDOW) round0 = max(0, q_block - window + 1) / (2 * KVB);
+  const int n_diag = Sq + Sk - 1;
+  const float* rbp = nullptr;
+  if constexpr (RELB) rbp = rel_bias + (int64_t)h * n_diag;
+  // lane's table entry for the first key of a round
+  const int rb_lane = (QBLK - 1) - (qg - q_block);
 
   for (int round = round0; round < n_rounds; ++round) {
     const int kvR = round * 2 * KVB;
     __syncthreads();
     stage_tile<2 * KVB, D, true, false>(k_lds, nullptr, kp, kvR, Sk, k_ss, tid);
     stage_tile<2 * KVB, D, false, true>(nullptr, v_lds, vp, kvR, Sk, v_ss, tid);
+    if constexpr (RELB) {
+      if (tid < FWD_DIAGS)
+        rb_lds[tid] =
+            relb_load(rbp, kvR - q_block - (QBLK - 1) + tid + (Sq - 1), n_diag) *
+            RELB_LOG2E;
+    }
     __syncthreads();
 
     for (int sub = 0; sub < 2; ++sub) {
@@ -356,6 +411,11 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
           const float off = (float)((r & 3) + 8 * (r >> 2));
           a = fmaf(slope2, rel0 + off, a);
           bb = fmaf(slope2, rel0 + (off + 32.f), bb);
+        }
+        if constexpr (RELB) {  // before the masks, as ALiBi
+          const int e = rb_lane + ro + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          a += rb_lds[e];
+          bb += rb_lds[e + 32];
         }
         if constexpr (MASKED) {
           if (kva >= sk_eff || (causal && kva > qg)) a = -3.0e38f;
@@ -494,7 +554,7 @@ __global__ void rowdot_kernel(const bf16_t* __restrict__ dout,
 // form of the plain instantiation (159 VGPRs, no scratch, K/V re-read from L2
 // per sub-tile) measured 2 % slower end to end (profiles/flash_tile_classes.md).
 // D=128 (128 accumulator VGPRs) re-reads K/V per use and sits at 244-256.
-template <int D, bool ALIBI, bool WINDOW>
+template <int D, bool ALIBI, bool WINDOW, bool RELB>
 __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
@@ -506,12 +566,18 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
     int64_t dk_sb, int64_t dk_ss, int64_t dk_sh, int64_t dv_sb, int64_t dv_ss,
     int64_t dv_sh, int H, int Sq, int Sk, float scale, float p_drop, uint64_t seed,
     int causal, int kv_group, const float* __restrict__ alibi_slopes,
-    int window) {
+    int window, const float* __restrict__ rel_bias) {
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
   // D=64: 64-row staging tiles.  D=128: 32-row tiles.
   constexpr int QTILE = (D == 64) ? 2 * QB : QB;
   constexpr int NSUB = QTILE / QB;
+  // RELB: the QBLK + QTILE - 1 diagonals of one staged q tile (natural
+  // domain), stored descending: entry (q - q0) + (QBLK - 1) - (kv - kv_block).
+  // A lane's registers walk q, so its lookups are one loop-invariant address
+  // plus non-negative immediates
+  constexpr int KV_DIAGS = QBLK + QTILE - 1;
+  __shared__ float rb_lds[RELB ? KV_DIAGS : 1];
 
   __shared__ __align__(16) bf16_t q_row[QTILE * D];
   __shared__ __align__(16) bf16_t q_tr[QTILE * D];
@@ -611,6 +677,12 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
   // ALiBi slope of THIS query head (the grid spans kv heads)
   float slope = 0.f;
   if constexpr (ALIBI) slope = alibi_slopes[h];
+  // relative-position row of THIS query head
+  const int n_diag = Sq + Sk - 1;
+  const float* rbp = nullptr;
+  if constexpr (RELB) rbp = rel_bias + (int64_t)h * n_diag;
+  // lane's table entry for the first row of a staged q tile
+  const float* rb_lane = rb_lds + ((QBLK - 1) - (kvg - kv_block) + 4 * hi);
 
   auto stage_all = [&](int qt) {
     const int q0 = qt * QTILE;
@@ -620,6 +692,11 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
       int qr = min(q0 + tid, Sq - 1);  // clamped: every staged row is readable
       lse_lds[tid] = lse[(int64_t)bh * Sq + qr];
       drow_lds[tid] = drow[(int64_t)bh * Sq + qr];
+    }
+    if constexpr (RELB) {
+      if (tid < KV_DIAGS)
+        rb_lds[tid] = relb_load(
+            rbp, kv_block - q0 + (QBLK - 1) - tid + (Sq - 1), n_diag);
     }
   };
 
@@ -688,6 +765,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
               &drow_lds[qbase - q0], 16);
           const float lse_r[4] = {lse4.x, lse4.y, lse4.z, lse4.w};
           const float drow_r[4] = {drow4.x, drow4.y, drow4.z, drow4.w};
+          const float* rb_run = rb_lane + (qbase - 4 * hi - q0);
           uint32_t hq = 0;
           if constexpr (DROP)  // == drop_hash4(.., qbase + (l31 & 3), kv4q)
             hq = rnd_hash_mix(
@@ -711,6 +789,8 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
             float x;
             if constexpr (ALIBI)
               x = fmaf(slope, (float)(kvg - qrow), s[r] * scale) - lse_r[j];
+            else if constexpr (RELB)  // a zero table gives the plain bits
+              x = fmaf(s[r], scale, rb_run[j] - lse_r[j]);
             else
               x = fmaf(s[r], scale, -lse_r[j]);
             float keep = 1.f;
@@ -791,7 +871,19 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
 // ===========================================================================
 // backward over q tiles: dQ   (block = 128 q rows, wave owns 32; fwd-like)
 // ===========================================================================
-template <int D, bool ALIBI, bool WINDOW>
+// RELB: this kernel also reduces the bias gradient, dS without `scale`
+// summed along diagonals.  A lane owns one query and its registers walk kv,
+// so for a fixed register the lanes of a wave hit consecutive diagonals.  A
+// sub-tile's 16 registers are first summed along the diagonals with lane
+// rotations (see ds_tile); the two LDS float atomics per lane that remain
+// collide two-way at most (hi = 0/1).  The sums live in a ring
+// indexed by the block diagonal a = kv + (QBLK - 1) - (q - q_block): the tile
+// at kv0 touches a in [kv0, kv0 + KVTILE + QBLK - 2], so once a tile is done
+// the diagonals below the next kv0 are complete.  They are flushed at the top
+// of the next staging round, between the two barriers the loop already has,
+// and the rest behind the loop: one global fp32 atomic per (workgroup,
+// touched diagonal), whatever the sequence length.
+template <int D, bool ALIBI, bool WINDOW, bool RELB>
 __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
@@ -802,7 +894,8 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
     int64_t do_sb, int64_t do_ss, int64_t do_sh, int64_t dq_sb, int64_t dq_ss,
     int64_t dq_sh, int H, int Sq, int Sk, float scale, float p_drop, uint64_t seed,
     int causal, int kv_group, const float* __restrict__ alibi_slopes,
-    int window) {
+    int window, const float* __restrict__ rel_bias,
+    float* __restrict__ d_rel_bias) {
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
   constexpr int KVTILE = (D == 64) ? 2 * QB : QB;
@@ -811,6 +904,12 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
   __shared__ __align__(16) bf16_t k_row[KVTILE * D];
   __shared__ __align__(16) bf16_t k_tr[KVTILE * D];
   __shared__ __align__(16) bf16_t v_row[KVTILE * D];
+  // RELB: the KVTILE + QBLK - 1 diagonals of one staged kv tile, entry
+  // (kv - kv0) + (QBLK - 1) - (q - q_block); and the ring of gradient sums
+  constexpr int Q_DIAGS = KVTILE + QBLK - 1;
+  static_assert(Q_DIAGS <= RELB_RING, "a tile's diagonals must fit the ring");
+  __shared__ float rb_lds[RELB ? Q_DIAGS : 1];
+  __shared__ float drb_lds[RELB ? RELB_RING : 1];
 
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -861,11 +960,30 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
   int tile0 = 0;
   if constexpr (WINDOW) tile0 = max(0, q_block - window + 1) / KVTILE;
 
+  const int n_diag = Sq + Sk - 1;
+  const float* rbp = nullptr;
+  float* drbp = nullptr;
+  if constexpr (RELB) {
+    rbp = rel_bias + (int64_t)h * n_diag;
+    drbp = d_rel_bias + (int64_t)h * n_diag;
+    drb_lds[tid] = 0.f;  // 256 threads, RELB_RING slots
+  }
+  // lane's table entry for the first key of a tile
+  const int rb_lane = (QBLK - 1) - (qg - q_block);
+  // global diagonal of a tile's entry 0, minus the tile's first key
+  const int rb_t0 = (Sq - 1) - q_block - (QBLK - 1);
+
   for (int tile = tile0; tile < n_tiles; ++tile) {
     const int kv0 = tile * KVTILE;
     __syncthreads();
     stage_tile<KVTILE, D, true, true>(k_row, k_tr, kp, kv0, Sk, k_ss, tid);
     stage_tile<KVTILE, D, true, false>(v_row, nullptr, vp, kv0, Sk, v_ss, tid);
+    if constexpr (RELB) {
+      if (tile > tile0)  // the diagonals the previous tile completed
+        relb_flush(drb_lds, drbp, tid, KVTILE, kv0 - KVTILE, rb_t0, n_diag);
+      if (tid < Q_DIAGS)
+        rb_lds[tid] = relb_load(rbp, kv0 + rb_t0 + tid, n_diag);
+    }
     __syncthreads();
 
     if (causal && kv0 > q_base + QB - 1) continue;
@@ -904,6 +1022,32 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
         // kv - q of this lane's first score (ALiBi)
         float rel0 = 0.f;
         if constexpr (ALIBI) rel0 = (float)(kv0s + 4 * hi - qg);
+        // RELB: the sub-tile's sums are formed in registers first.  Register r
+        // of lane l31 sits on diagonal (register 0's) + sh - l31 with
+        // sh = (r & 3) + 8 * (r >> 2), so rotating it down by sh lanes inside
+        // the 32-lane half puts it on the receiving lane's register-0
+        // diagonal, or 32 above it where the rotation wrapped.  Two LDS
+        // atomics per lane and sub-tile then replace sixteen, which measured
+        // 6x the whole plain kernel.  D=128 has no registers for the fifteen
+        // rotation addresses (256 VGPRs, 40 B/lane of scratch, reloads in the
+        // tile loop) and keeps one atomic per element.
+        constexpr bool PRE_REDUCE = D == 64;
+        // register 0's block diagonal in the gradient ring
+        const int slot0 = (rb_lane + kv0s + 4 * hi) & (RELB_RING - 1);
+        float g_main = 0.f, g_wrap = 0.f;
+        auto diag_add = [&](int r, float gv) {
+          const int sh = (r & 3) + 8 * (r >> 2);
+          if constexpr (!PRE_REDUCE) {
+            atomicAdd(&drb_lds[(slot0 + sh) & (RELB_RING - 1)], gv);
+          } else if (sh == 0) {
+            g_main = gv;
+          } else {
+            const float t = __shfl(gv, ((l31 + sh) & 31) | (lane & 32));
+            const bool wrapped = l31 + sh >= 32;
+            g_main += wrapped ? 0.f : t;
+            g_wrap += wrapped ? t : 0.f;
+          }
+        };
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) {
           const int kvb = kv0s + 8 * r4 + 4 * hi;  // 4-aligned kv run
@@ -915,23 +1059,41 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
             const int r = r4 * 4 + j;
             const int kv = kvb + j;
             float x;  // scale * s (+ bias) - lse, the exp argument
+            // this element's table entry (in range for every lane)
+            int e = 0;
+            if constexpr (RELB) e = rb_lane + (kv - kv0);
             if constexpr (ALIBI)
               x = fmaf(slope, rel0 + (float)(8 * r4 + j), st[r] * scale) - lse_lane;
+            else if constexpr (RELB)  // a zero table gives the plain bits
+              x = fmaf(st[r], scale, rb_lds[e] - lse_lane);
             else
               x = fmaf(st[r], scale, -lse_lane);
+            // RELB: dS without `scale` goes to the diagonal's sum (the bias
+            // enters after the scaling, so `scale` must not reach it)
             if constexpr (MASKED) {
               bool valid = kv < sk_eff && qg < Sq && (!causal || kv <= qg);
               if constexpr (WINDOW) valid = valid && (qg - kv < window);
               const uint32_t vm = valid ? 0xFFFFFFFFu : 0u;
               float p = and_f32(__expf(x), vm);
               float keep = (p_drop > 0.f) ? drop_keep_byte(h, j, thr8, ks) : 1.f;
-              ds[r] = and_f32(scale * p * fmaf(dpdt[r], keep, -drow_lane), vm);
+              // (scale * p) * dd, the product formed first as it always was
+              const float sp = scale * p;
+              const float dd = fmaf(dpdt[r], keep, -drow_lane);
+              ds[r] = and_f32(sp * dd, vm);
+              if constexpr (RELB) diag_add(r, and_f32(p * dd, vm));
             } else {
               float p = __expf(x);
               float keep = (p_drop > 0.f) ? drop_keep_byte(h, j, thr8, ks) : 1.f;
-              ds[r] = scale * p * fmaf(dpdt[r], keep, -drow_lane);
+              const float sp = scale * p;
+              const float dd = fmaf(dpdt[r], keep, -drow_lane);
+              ds[r] = sp * dd;
+              if constexpr (RELB) diag_add(r, p * dd);
             }
           }
+        }
+        if constexpr (RELB && PRE_REDUCE) {  // slot0 and the one 32 above it
+          atomicAdd(&drb_lds[slot0], g_main);
+          atomicAdd(&drb_lds[(slot0 + 32) & (RELB_RING - 1)], g_wrap);
         }
       };
       if (interior) ds_tile(std::false_type{});
@@ -952,6 +1114,13 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
       }
       PRIO_LO();
     }
+  }
+
+  if constexpr (RELB) {  // the diagonals still open after the last tile
+    __syncthreads();
+    if (n_tiles > tile0)
+      relb_flush(drb_lds, drbp, tid, Q_DIAGS, (n_tiles - 1) * KVTILE, rb_t0,
+                 n_diag);
   }
 
   if (qg < Sq) {
@@ -997,30 +1166,37 @@ extern "C" void flash_fwd_bf16(const void* q, const void* k, const void* v, void
                                int64_t o_sh, int B, int H, int Sq, int Sk, int D,
                                float scale, float p_drop, uint64_t seed, int causal,
                                int kv_group, const float* alibi_slopes,
-                               int window, hipStream_t stream) {
+                               int window, const float* rel_bias,
+                               hipStream_t stream) {
   dim3 grid(CDIV(Sq, QBLK), B * H);
   dim3 block(256);
 #define FWD_ARGS                                                                     \
   (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, kv_len,     \
       q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, o_sb, o_ss, o_sh, H, Sq, \
-      Sk, scale, p_drop, seed, causal, kv_group, alibi_slopes, window
-  // the binding rejects window together with ALiBi: no cross product
+      Sk, scale, p_drop, seed, causal, kv_group, alibi_slopes, window, rel_bias
+  // the binding rejects window, ALiBi and a relative-position table in any
+  // combination: no cross product
   const bool alibi = alibi_slopes != nullptr;
+  const bool relb = rel_bias != nullptr;
   window = window > 0 ? min(window, max(Sq, Sk)) : 0;  // same mask, no overflow
   if (D == 64) {
     if (alibi)
-      flash_fwd_kernel<64, true, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<64, true, false, false><<<grid, block, 0, stream>>>(FWD_ARGS);
     else if (window > 0)
-      flash_fwd_kernel<64, false, true><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<64, false, true, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+    else if (relb)
+      flash_fwd_kernel<64, false, false, true><<<grid, block, 0, stream>>>(FWD_ARGS);
     else
-      flash_fwd_kernel<64, false, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<64, false, false, false><<<grid, block, 0, stream>>>(FWD_ARGS);
   } else if (D == 128) {
     if (alibi)
-      flash_fwd_kernel<128, true, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<128, true, false, false><<<grid, block, 0, stream>>>(FWD_ARGS);
     else if (window > 0)
-      flash_fwd_kernel<128, false, true><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<128, false, true, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+    else if (relb)
+      flash_fwd_kernel<128, false, false, true><<<grid, block, 0, stream>>>(FWD_ARGS);
     else
-      flash_fwd_kernel<128, false, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<128, false, false, false><<<grid, block, 0, stream>>>(FWD_ARGS);
   }
 #undef FWD_ARGS
 }
@@ -1035,7 +1211,8 @@ extern "C" void flash_bwd_bf16(
     int64_t dq_ss, int64_t dq_sh, int64_t dk_sb, int64_t dk_ss, int64_t dk_sh,
     int64_t dv_sb, int64_t dv_ss, int64_t dv_sh, int B, int H, int Sq, int Sk, int D,
     float scale, float p_drop, uint64_t seed, int causal, int kv_group,
-    const float* alibi_slopes, int window, hipStream_t stream) {
+    const float* alibi_slopes, int window, const float* rel_bias,
+    float* d_rel_bias, hipStream_t stream) {
   // Drow = rowsum(dO * O)  (dO and O share layout; use dO's strides for both:
   // the wrapper guarantees o was allocated with the same layout)
   {
@@ -1057,30 +1234,34 @@ extern "C" void flash_bwd_bf16(
       drow_ws, kv_len, (bf16_t*)dk, (bf16_t*)dv, q_sb, q_ss, q_sh, k_sb, k_ss,       \
       k_sh, v_sb, v_ss, v_sh, do_sb, do_ss, do_sh, dk_sb, dk_ss, dk_sh, dv_sb,       \
       dv_ss, dv_sh, H, Sq, Sk, scale, p_drop, seed, causal, kv_group,                \
-      alibi_slopes, window
+      alibi_slopes, window, rel_bias
 #define BWD_ARGS_Q                                                                   \
   (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse,    \
       drow_ws, kv_len, (bf16_t*)dq, q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss,  \
       v_sh, do_sb, do_ss, do_sh, dq_sb, dq_ss, dq_sh, H, Sq, Sk, scale, p_drop,      \
-      seed, causal, kv_group, alibi_slopes, window
+      seed, causal, kv_group, alibi_slopes, window, rel_bias, d_rel_bias
   dim3 block(256);
   const int Hkv = H / kv_group;  // bwd_kv grid spans the KV heads
   const dim3 grid_kv(CDIV(Sk, QBLK), B * Hkv), grid_q(CDIV(Sq, QBLK), B * H);
-#define BWD_LAUNCH(DD, AL, WIN)                                                      \
+#define BWD_LAUNCH(DD, AL, WIN, RB)                                                  \
   do {                                                                               \
-    flash_bwd_kv_kernel<DD, AL, WIN><<<grid_kv, block, 0, stream>>>(BWD_ARGS_KV);    \
-    flash_bwd_q_kernel<DD, AL, WIN><<<grid_q, block, 0, stream>>>(BWD_ARGS_Q);       \
+    flash_bwd_kv_kernel<DD, AL, WIN, RB>                                             \
+        <<<grid_kv, block, 0, stream>>>(BWD_ARGS_KV);                                \
+    flash_bwd_q_kernel<DD, AL, WIN, RB><<<grid_q, block, 0, stream>>>(BWD_ARGS_Q);   \
   } while (0)
   const bool alibi = alibi_slopes != nullptr;
+  const bool relb = rel_bias != nullptr;
   window = window > 0 ? min(window, max(Sq, Sk)) : 0;  // same mask, no overflow
   if (D == 64) {
-    if (alibi) BWD_LAUNCH(64, true, false);
-    else if (window > 0) BWD_LAUNCH(64, false, true);
-    else BWD_LAUNCH(64, false, false);
+    if (alibi) BWD_LAUNCH(64, true, false, false);
+    else if (window > 0) BWD_LAUNCH(64, false, true, false);
+    else if (relb) BWD_LAUNCH(64, false, false, true);
+    else BWD_LAUNCH(64, false, false, false);
   } else if (D == 128) {
-    if (alibi) BWD_LAUNCH(128, true, false);
-    else if (window > 0) BWD_LAUNCH(128, false, true);
-    else BWD_LAUNCH(128, false, false);
+    if (alibi) BWD_LAUNCH(128, true, false, false);
+    else if (window > 0) BWD_LAUNCH(128, false, true, false);
+    else if (relb) BWD_LAUNCH(128, false, false, true);
+    else BWD_LAUNCH(128, false, false, false);
   }
 #undef BWD_LAUNCH
 }

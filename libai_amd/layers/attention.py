@@ -34,6 +34,17 @@ def _dummy_tab(device):
     if key not in _DUMMY_TABS:
         _DUMMY_TABS[key] = torch.zeros(1, dtype=torch.float32, device=device)
     return _DUMMY_TABS[key]
+
+
+def _rel_table_fits(table, num_heads, s, device):
+    """A relative-position table is fused only if it was built for exactly
+    this call: [heads of this rank, 2s - 1] fp32 on the activations' device.
+    Anything else keeps the materialized bias."""
+    return (
+        table.dtype == torch.float32
+        and table.device == device
+        and tuple(table.shape) == (num_heads, 2 * s - 1)
+    )
 from ..utils import distributed as du
 from .linear import Linear1D
 
@@ -159,12 +170,16 @@ class MultiheadAttention(nn.Module):
 
         # an ALiBi bias from build_alibi_bias carries its fp32 slopes: the
         # fused kernels add slope * (kv - q) in-register and never read the
-        # tensor.  Any other bias (T5, user-supplied) has no slopes and takes
-        # the materialized path below.
-        from ..ops.attention import bias_alibi_slopes
+        # tensor.  A T5 relative-position bias carries its fp32 diagonal table:
+        # the flash kernels add table[h, kv - q + s - 1] and return the table
+        # gradient (training / no-cache path only; the decode kernels take no
+        # table).  Any other bias (Swin, user-supplied, a sliced T5 bias) has
+        # neither attribute and takes the materialized path below.
+        from ..ops.attention import bias_alibi_slopes, bias_rel_table
 
         slopes = bias_alibi_slopes(position_bias)
         bias_fusable = position_bias is None or slopes is not None
+        rel_table = bias_rel_table(position_bias) if slopes is None else None
 
         # fused flash path: consumes the qkv buffer with ZERO copies (strided
         # [b, s, nh, hs] views), O lands directly in [b, s, h] layout.
@@ -172,7 +187,7 @@ class MultiheadAttention(nn.Module):
             not self.is_cross_attention
             and past_key_value is None
             and not use_cache
-            and bias_fusable
+            and (bias_fusable or rel_table is not None)
         ):
             from ..ops.attention import (
                 flash_attention_available,
@@ -186,7 +201,9 @@ class MultiheadAttention(nn.Module):
             if flash_attention_available(
                 self.head_size, hidden_states.dtype, hidden_states.device, s, s,
                 attention_mask,
-            ):
+            ) and (rel_table is None or _rel_table_fits(
+                rel_table, self.num_heads_local, s, hidden_states.device
+            )):
                 qkv = self.query_key_value(hidden_states)
                 qkv5 = qkv.view(b, s, self.num_heads_local, 3, self.head_size)
                 o = flash_attention_qkv(
@@ -197,6 +214,7 @@ class MultiheadAttention(nn.Module):
                     training=self.training,
                     kv_len=mask_kv_len(attention_mask),
                     alibi_slopes=slopes,
+                    rel_bias=rel_table,
                 )
                 context = o.reshape(b, s, self.num_heads_local * self.head_size)
                 out, bias = self.dense(context)

@@ -71,7 +71,18 @@ class T5RelativePositionBias(nn.Module):
         buckets = self._bucket(mem - ctx, self.bidirectional, self.num_buckets,
                                self.max_distance)  # [sq, sk]
         vals = self.weight[buckets]  # [sq, sk, nh_local]
-        return vals.permute(2, 0, 1).unsqueeze(0).to(self.weight.dtype)
+        bias = vals.permute(2, 0, 1).unsqueeze(0).to(self.weight.dtype)
+        # The bias is Toeplitz: bias[0, h, i, j] depends on h and j - i only.
+        # Its fp32 diagonal table [nh_local, sq + sk - 1], entry j - i + sq - 1,
+        # rides along as ``bias._rel_bias_table`` (the convention of
+        # ``_alibi_slopes``): attention layers that see it hand the table to
+        # the flash kernels, whose backward returns the table gradient, and
+        # autograd maps that back to the weight through the gather below.
+        delta = torch.arange(-(sq - 1), sk, device=device)
+        dbuckets = self._bucket(delta, self.bidirectional, self.num_buckets,
+                                self.max_distance)  # [sq + sk - 1]
+        bias._rel_bias_table = self.weight.float()[dbuckets].t().contiguous()
+        return bias
 
 
 def alibi_slopes(num_heads):

@@ -19,6 +19,14 @@ key j iff j <= i and i - j < W, HF's ``q_idx - kv_idx < sliding_window``).
 The kernels mask in-register and skip every tile below the band.  ``None`` or
 0 means off; a window covering the whole sequence is normalized to off.
 
+Relative-position bias (T5/MT5): an optional fp32 ``rel_bias`` [H, Sq+Sk-1]
+(one row per query head) makes the kernels add rel_bias[h, kv - q + Sq - 1]
+to every pre-softmax score in-register.  The bias is Toeplitz, so the
+[H, Sq, Sk] tensor never exists; the table is learned, so the backward also
+returns its gradient (dS without the scale, summed along diagonals with fp32
+atomics: summation-order dependent in its last bits, like the embedding
+backward).  Not combinable with ``alibi_slopes`` or ``window``.
+
 Replaces the reference's K2-K5 chain (reference
 libai/layers/attention.py:211-253).
 """
@@ -28,7 +36,7 @@ import torch
 from ._ext import draw_seed, ext
 
 __all__ = ["flash_attention", "flash_attention_qkv", "flash_attention_available",
-           "mask_kv_len", "bias_alibi_slopes"]
+           "mask_kv_len", "bias_alibi_slopes", "bias_rel_table"]
 
 
 def mask_kv_len(pad_mask):
@@ -43,6 +51,26 @@ def bias_alibi_slopes(position_bias):
     if position_bias is None:
         return None
     return getattr(position_bias, "_alibi_slopes", None)
+
+
+def bias_rel_table(position_bias):
+    """The fp32 [nh, sq + sk - 1] diagonal table attached to a bias by
+    ``T5RelativePositionBias`` (the bias is then exactly Toeplitz and the
+    kernels can fuse it, gradient included), else None."""
+    if position_bias is None:
+        return None
+    return getattr(position_bias, "_rel_bias_table", None)
+
+
+def _rel_bias_arg(rel_bias, alibi_slopes, window):
+    """Rejects a relative-position table together with ALiBi or a window."""
+    if rel_bias is None:
+        return None
+    if alibi_slopes is not None:
+        raise ValueError("rel_bias cannot be combined with alibi_slopes")
+    if window is not None and window != 0:
+        raise ValueError("rel_bias cannot be combined with a sliding window")
+    return rel_bias
 
 
 def _window_arg(window, n_keys, causal=True, alibi_slopes=None):
@@ -81,14 +109,18 @@ class _FlashAttnQKVFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv5, scale, p_drop, causal, kv_len, alibi_slopes=None,
-                window=0):
+                window=0, rel_bias=None):
         q = qkv5[..., 0, :]
         k = qkv5[..., 1, :]
         v = qkv5[..., 2, :]
         seed = draw_seed() if p_drop > 0 else 0
         o, lse = ext().flash_fwd(q, k, v, scale, p_drop, seed, causal, kv_len,
-                                 alibi_slopes, window)
-        ctx.save_for_backward(qkv5, o, lse)
+                                 alibi_slopes, window, rel_bias)
+        if rel_bias is None:
+            ctx.save_for_backward(qkv5, o, lse)
+        else:
+            ctx.save_for_backward(qkv5, o, lse, rel_bias)
+        ctx.has_rel_bias = rel_bias is not None
         ctx.kv_len = kv_len
         ctx.alibi_slopes = alibi_slopes  # constant: no grad flows to it
         ctx.window = window
@@ -97,38 +129,48 @@ class _FlashAttnQKVFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, do):
-        qkv5, o, lse = ctx.saved_tensors
+        qkv5, o, lse, *rest = ctx.saved_tensors
+        rel_bias = rest[0] if ctx.has_rel_bias else None
         scale, p_drop, seed, causal = ctx.meta
         dqkv = torch.empty_like(qkv5)
-        ext().flash_bwd(
+        grads = ext().flash_bwd(
             qkv5[..., 0, :], qkv5[..., 1, :], qkv5[..., 2, :], o, do.contiguous(),
             lse, scale, p_drop, seed, causal, dqkv, ctx.kv_len,
-            ctx.alibi_slopes, ctx.window,
+            ctx.alibi_slopes, ctx.window, rel_bias,
         )
-        return dqkv, None, None, None, None, None, None
+        d_rel = grads[3] if rel_bias is not None and ctx.needs_input_grad[7] else None
+        return dqkv, None, None, None, None, None, None, d_rel
 
 
 def flash_attention_qkv(qkv5, scale, p_drop=0.0, causal=True, training=True,
-                        kv_len=None, alibi_slopes=None, window=None):
+                        kv_len=None, alibi_slopes=None, window=None,
+                        rel_bias=None):
     """qkv5: packed [B, S, H, 3, D] bf16 -> O [B, S, H, D] (zero-copy in/out).
 
     kv_len: optional int32 [B] — keys at/after kv_len[b] are masked out.
     alibi_slopes: optional fp32 [H] — adds slope[h] * (kv - q) to the scores.
-    window: optional int W — causal sliding window over the last W keys."""
+    window: optional int W — causal sliding window over the last W keys.
+    rel_bias: optional fp32 [H, 2S-1] — adds rel_bias[h, kv - q + S - 1] to the
+    scores; differentiable (not combinable with alibi_slopes or window)."""
+    rel_bias = _rel_bias_arg(rel_bias, alibi_slopes, window)
     window = _window_arg(window, qkv5.shape[1], causal, alibi_slopes)
     return _FlashAttnQKVFn.apply(qkv5, scale, p_drop if training else 0.0, causal,
-                                 kv_len, alibi_slopes, window)
+                                 kv_len, alibi_slopes, window, rel_bias)
 
 
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale, p_drop, causal, kv_len, alibi_slopes=None,
-                window=0):
+                window=0, rel_bias=None):
         # q, k, v: [B, S, H, D] (may be strided views of the fused qkv buffer)
         seed = draw_seed() if p_drop > 0 else 0
         o, lse = ext().flash_fwd(q, k, v, scale, p_drop, seed, causal, kv_len,
-                                 alibi_slopes, window)
-        ctx.save_for_backward(q, k, v, o, lse)
+                                 alibi_slopes, window, rel_bias)
+        if rel_bias is None:
+            ctx.save_for_backward(q, k, v, o, lse)
+        else:
+            ctx.save_for_backward(q, k, v, o, lse, rel_bias)
+        ctx.has_rel_bias = rel_bias is not None
         ctx.kv_len = kv_len
         ctx.alibi_slopes = alibi_slopes
         ctx.window = window
@@ -137,25 +179,32 @@ class _FlashAttnFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse = ctx.saved_tensors
+        q, k, v, o, lse, *rest = ctx.saved_tensors
+        rel_bias = rest[0] if ctx.has_rel_bias else None
         scale, p_drop, seed, causal = ctx.meta
-        dq, dk, dv = ext().flash_bwd(
+        grads = ext().flash_bwd(
             q, k, v, o, do.contiguous(), lse, scale, p_drop, seed, causal, None,
-            ctx.kv_len, ctx.alibi_slopes, ctx.window,
+            ctx.kv_len, ctx.alibi_slopes, ctx.window, rel_bias,
         )
-        return dq, dk, dv, None, None, None, None, None, None
+        dq, dk, dv = grads[:3]
+        d_rel = grads[3] if rel_bias is not None and ctx.needs_input_grad[9] else None
+        return dq, dk, dv, None, None, None, None, None, None, d_rel
 
 
 def flash_attention(q, k, v, scale, p_drop=0.0, causal=True, training=True,
-                    kv_len=None, alibi_slopes=None, window=None):
+                    kv_len=None, alibi_slopes=None, window=None, rel_bias=None):
     """q, k, v: [B, S, H, D] bf16 -> O [B, S, H, D].
 
     alibi_slopes: optional fp32 [H] (query heads) — fused ALiBi bias.
     window: optional int W — causal sliding window: query i sees the keys
-    j <= i with i - j < W (not combinable with alibi_slopes or causal=False)."""
+    j <= i with i - j < W (not combinable with alibi_slopes or causal=False).
+    rel_bias: optional fp32 [H, Sq+Sk-1] (query heads) — fused Toeplitz bias
+    rel_bias[h, kv - q + Sq - 1]; differentiable (its gradient is summed over
+    the batch), not combinable with alibi_slopes or window."""
+    rel_bias = _rel_bias_arg(rel_bias, alibi_slopes, window)
     window = _window_arg(window, k.shape[1], causal, alibi_slopes)
     return _FlashAttnFn.apply(q, k, v, scale, p_drop if training else 0.0, causal,
-                              kv_len, alibi_slopes, window)
+                              kv_len, alibi_slopes, window, rel_bias)
 
 
 def decode_attention_available(q, head_dim):
