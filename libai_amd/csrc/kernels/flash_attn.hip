@@ -218,6 +218,19 @@ __device__ __forceinline__ float drop_keep(uint64_t seed, uint64_t bh, int64_t S
   return drop_keep_byte(h, kv & 3, thr8, ks);
 }
 
+// Which tile a workgroup works on.  Workgroups are dealt round-robin over the
+// chip's 8 XCDs by their linear id x + gridDim.x * y, so with the plain map
+// tile = blockIdx.x and 8 tiles per (batch, head) (S = 1024) every XCD gets
+// ONE tile index of every head.  Under `causal` a tile's work grows linearly
+// with its index (forward, bwd_q) or falls with it (bwd_kv), so one XCD then
+// gets all the heaviest tiles, 16/9 of the mean, and the kernel lasts as long
+// as that XCD.  Rotating the tile index by the head index deals every XCD
+// every tile index in turn.  Only the assignment of tiles to workgroups
+// changes: every tile is computed as before, bit for bit.
+__device__ __forceinline__ int block_tile() {
+  return (int)((blockIdx.x + blockIdx.y) % gridDim.x);
+}
+
 // ===========================================================================
 // forward
 // ===========================================================================
@@ -300,7 +313,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
 
   const int bh = blockIdx.y;
   const int b = bh / H, h = bh % H;
-  const int q_block = blockIdx.x * QBLK;
+  const int q_block = block_tile() * QBLK;
   // wave-uniform by construction; readfirstlane tells the compiler, so the
   // sub-tile skips and the tile-class test become scalar branches
   const int q_base = __builtin_amdgcn_readfirstlane(q_block + wave * QB);
@@ -554,6 +567,20 @@ __global__ void rowdot_kernel(const bf16_t* __restrict__ dout,
 // form of the plain instantiation (159 VGPRs, no scratch, K/V re-read from L2
 // per sub-tile) measured 2 % slower end to end (profiles/flash_tile_classes.md).
 // D=128 (128 accumulator VGPRs) re-reads K/V per use and sits at 244-256.
+//
+// q-tile loop.  D=128 has no register left and keeps the plain form
+//   for each q tile: barrier; stage; barrier; compute.
+// D=64 (PIPE) prefetches on the registers that 2 waves/SIMD leave free: the
+// global loads of tile qt+1 (Q, dO, lse, Drow and the RELB diagonals: 18-19
+// VGPRs) are issued before the compute of tile qt and stored to LDS after it,
+//   stage(first); barrier;
+//   for each q tile: load(next); compute; barrier; write(next); barrier
+// so their latency hides under 32 MFMAs per wave and the exp/dropout work.
+// (stage() itself waits for each 16-byte load before it issues the next one:
+// five round trips per tile in the plain form.)  The pipeline drains and
+// restarts per GQA query head; all its conditions are workgroup-uniform.  The
+// staged values, the compute body and their order are those of the plain
+// loop, so dK and dV do not change by a bit.
 template <int D, bool ALIBI, bool WINDOW, bool RELB>
 __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
@@ -587,6 +614,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
   // q rows, so each run takes its lse/Drow with one unconditional ds_read_b128
   __shared__ __align__(16) float lse_lds[QTILE];
   __shared__ __align__(16) float drow_lds[QTILE];
+  constexpr bool PIPE = D == 64;
 
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -599,7 +627,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
   const int Hkv = H / kv_group;
   const int bhk = blockIdx.y;
   const int b = bhk / Hkv, hk = bhk % Hkv;
-  const int kv_block = blockIdx.x * QBLK;   // 128 kv rows per block
+  const int kv_block = block_tile() * QBLK;   // 128 kv rows per block
   // this wave's 32 kv rows; wave-uniform (scalar skips and tile-class branch)
   const int kv_base = __builtin_amdgcn_readfirstlane(kv_block + wave * QB);
   const int kvg = kv_base + l31;            // lane's kv row
@@ -699,6 +727,66 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
             rbp, kv_block - q0 + (QBLK - 1) - tid + (Sq - 1), n_diag);
     }
   };
+
+  // PIPE: stage_all split in two.  load_tile issues the global loads of tile
+  // qt into registers (same clamping: rows >= Sq are zeros, lse/Drow and the
+  // diagonals read a clamped neighbour) and does not wait for them;
+  // write_tile stores them to LDS, which is where the wait for them lands.
+  constexpr int PF = QTILE * D / 8 / 256;  // 16B chunks per thread and tensor
+  bf16x8_t pf_q[PF], pf_do[PF];
+  float pf_lse = 0.f, pf_drow = 0.f, pf_rb = 0.f;
+  auto load_tile = [&](int qt) {
+    const int q0 = qt * QTILE;
+#pragma unroll
+    for (int cc = 0; cc < PF; ++cc) {
+      const int flat = tid + cc * 256;
+      const int gr = q0 + flat / (D / 8);
+      const int col8 = flat % (D / 8);
+      pf_q[cc] = (gr < Sq)
+                     ? *(const bf16x8_t*)(qp + (int64_t)gr * q_ss + col8 * 8)
+                     : bf16x8_t{};
+      pf_do[cc] = (gr < Sq)
+                      ? *(const bf16x8_t*)(dop + (int64_t)gr * do_ss + col8 * 8)
+                      : bf16x8_t{};
+    }
+    if (tid < QTILE) {
+      int qr = min(q0 + tid, Sq - 1);
+      pf_lse = lse[(int64_t)bh * Sq + qr];
+      pf_drow = drow[(int64_t)bh * Sq + qr];
+    }
+    if constexpr (RELB) {
+      if (tid < KV_DIAGS)
+        pf_rb = relb_load(
+            rbp, kv_block - q0 + (QBLK - 1) - tid + (Sq - 1), n_diag);
+    }
+  };
+  auto write_tile = [&] {
+#pragma unroll
+    for (int cc = 0; cc < PF; ++cc) {
+      const int flat = tid + cc * 256;
+      const int row = flat / (D / 8);
+      const int col8 = flat % (D / 8);
+      row_img_write<D>(q_row, row, col8, pf_q[cc]);
+      tr_img_write<D>(q_tr, row, col8 * 8, pf_q[cc]);
+      row_img_write<D>(do_row, row, col8, pf_do[cc]);
+      tr_img_write<D>(do_tr, row, col8 * 8, pf_do[cc]);
+    }
+    if (tid < QTILE) {
+      lse_lds[tid] = pf_lse;
+      drow_lds[tid] = pf_drow;
+    }
+    if constexpr (RELB) {
+      if (tid < KV_DIAGS) rb_lds[tid] = pf_rb;
+    }
+  };
+  // s_waitcnt vmcnt(0) alone (expcnt and lgkmcnt fields all ones).  Placed
+  // where no load is in flight any more, so it costs nothing; it tells the
+  // compiler on EVERY path into compute_tile that the K/V fragment loads from
+  // the kernel's top are done.  Without it the path that issues no prefetch
+  // (last tile) leaves them pending in the compiler's model, and the counted
+  // waits it then puts in front of the S/dPd MFMAs (vmcnt(7) ... vmcnt(0))
+  // also wait for the prefetch that was issued behind them.
+  auto vm_drain = [] { __builtin_amdgcn_s_waitcnt(0x0F70); };
 
   auto compute_tile = [&](int q0) {
     if (causal && q0 + QTILE - 1 < kv_base) return;  // entirely above diag
@@ -839,11 +927,32 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
     }
   };  // compute_tile
 
-  for (int qt = qt_start; qt < n_qtiles; ++qt) {
-    __syncthreads();
-    stage_all(qt);
-    __syncthreads();
-    compute_tile(qt * QTILE);
+  if constexpr (PIPE) {
+    // n_qtiles == 0 (fully padded kv block) and a window that ends the loop
+    // early skip whole iterations: qt_start and n_qtiles are workgroup-uniform
+    if (qt_start < n_qtiles) {
+      // the images are free: the previous head's last compute ended in a barrier
+      stage_all(qt_start);
+      __syncthreads();
+    }
+    for (int qt = qt_start; qt < n_qtiles; ++qt) {
+      const bool more = qt + 1 < n_qtiles;
+      vm_drain();
+      if (more) load_tile(qt + 1);
+      compute_tile(qt * QTILE);
+      __syncthreads();  // every wave has read tile qt
+      if (more) {
+        write_tile();
+        __syncthreads();
+      }
+    }
+  } else {
+    for (int qt = qt_start; qt < n_qtiles; ++qt) {
+      __syncthreads();
+      stage_all(qt);
+      __syncthreads();
+      compute_tile(qt * QTILE);
+    }
   }
 
   }  // group loop (GQA)
@@ -919,7 +1028,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
 
   const int bh = blockIdx.y;
   const int b = bh / H, h = bh % H;
-  const int q_block = blockIdx.x * QBLK;
+  const int q_block = block_tile() * QBLK;
   // wave-uniform: scalar sub-tile skips and tile-class branch (see forward)
   const int q_base = __builtin_amdgcn_readfirstlane(q_block + wave * QB);
   const int qg = q_base + l31;
