@@ -103,7 +103,7 @@ void flash_fwd_bf16(const void*, const void*, const void*, void*, float*,
                     const int*, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int, int, int, int, int, float, float, uint64_t, int, int,
-                    const float*, int, const float*, hipStream_t);
+                    const float*, int, const float*, const int*, hipStream_t);
 void flash_bwd_bf16(const void*, const void*, const void*, const void*, const void*,
                     const float*, float*, const int*, void*, void*, void*, int64_t,
                     int64_t,
@@ -111,7 +111,8 @@ void flash_bwd_bf16(const void*, const void*, const void*, const void*, const vo
                     int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                     int64_t, int, int, int, int, int, float, float, uint64_t, int,
-                    int, const float*, int, const float*, float*, hipStream_t);
+                    int, const float*, int, const float*, float*, const int*,
+                    const int*, hipStream_t);
 void attn_dropout_apply_bf16(void*, int64_t, int64_t, int64_t, float, uint64_t,
                              hipStream_t);
 void attn_dropout_apply_f32(void*, int64_t, int64_t, int64_t, float, uint64_t,
@@ -139,16 +140,16 @@ void flash_decode_split_bf16(const void*, const void*, const void*, void*,
                              hipStream_t);
 void rope_fwd_bf16(const void*, void*, const float*, const float*, int64_t, int64_t,
                    int64_t, int64_t, int64_t, int64_t, int, int, int, int, int,
-                   hipStream_t);
+                   const int*, int, hipStream_t);
 void rope_fwd_f32(const void*, void*, const float*, const float*, int64_t, int64_t,
                   int64_t, int64_t, int64_t, int64_t, int, int, int, int, int,
-                  hipStream_t);
+                  const int*, int, hipStream_t);
 void rope_bwd_bf16(const void*, void*, const float*, const float*, int64_t, int64_t,
                    int64_t, int64_t, int64_t, int64_t, int, int, int, int, int,
-                   hipStream_t);
+                   const int*, int, hipStream_t);
 void rope_bwd_f32(const void*, void*, const float*, const float*, int64_t, int64_t,
                   int64_t, int64_t, int64_t, int64_t, int, int, int, int, int,
-                  hipStream_t);
+                  const int*, int, hipStream_t);
 void rope_kv_insert_bf16(const void*, const void*, const void*, void*, void*,
                          void*, const float*, const float*, const long long*,
                          int, int, int, int, int64_t, int64_t, int64_t, int64_t,
@@ -470,6 +471,39 @@ static const float* rel_bias_ptr(const c10::optional<torch::Tensor>& table,
   return table->data_ptr<float>();
 }
 
+// optional packed-document bounds: int32 [B, Sq] each, doc_start[b][i] the
+// first token of the document holding token i, doc_end[b][i] one past its
+// last.  Causal self-attention only; not combinable with ALiBi, a window or
+// a relative-position table.  Sets both pointers, or neither.
+static void doc_bounds_ptrs(const c10::optional<torch::Tensor>& doc_start,
+                            const c10::optional<torch::Tensor>& doc_end,
+                            const torch::Tensor& q, int64_t B, int64_t Sq,
+                            int64_t Sk, bool causal, bool has_alibi,
+                            int64_t window, bool has_rel_bias, const char* op,
+                            const int** ds, const int** de) {
+  *ds = nullptr;
+  *de = nullptr;
+  TORCH_CHECK(doc_start.has_value() == doc_end.has_value(), op,
+              ": doc_start and doc_end must be given together");
+  if (!doc_start.has_value()) return;
+  TORCH_CHECK(causal, op, ": document bounds require causal attention");
+  TORCH_CHECK(Sq == Sk, op, ": document bounds need Sq == Sk");
+  TORCH_CHECK(!has_alibi, op,
+              ": document bounds cannot be combined with alibi_slopes");
+  TORCH_CHECK(window == 0, op,
+              ": document bounds cannot be combined with a sliding window");
+  TORCH_CHECK(!has_rel_bias, op,
+              ": document bounds cannot be combined with rel_bias");
+  for (const torch::Tensor* t : {&doc_start.value(), &doc_end.value()})
+    TORCH_CHECK(t->scalar_type() == torch::kInt32 && t->is_cuda() &&
+                    t->get_device() == q.get_device() && t->is_contiguous() &&
+                    t->dim() == 2 && t->size(0) == B && t->size(1) == Sq,
+                op, ": doc_start / doc_end must be contiguous int32 tensors of "
+                "shape [B, Sq] on q's device");
+  *ds = doc_start->data_ptr<int>();
+  *de = doc_end->data_ptr<int>();
+}
+
 // ---------------------------------------------------------------------------
 // fused single-query decode attention (K16 serving path)
 // ---------------------------------------------------------------------------
@@ -577,7 +611,9 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
                                                    c10::optional<torch::Tensor> kv_len,
                                                    c10::optional<torch::Tensor> alibi_slopes,
                                                    int64_t window,
-                                                   c10::optional<torch::Tensor> rel_bias) {
+                                                   c10::optional<torch::Tensor> rel_bias,
+                                                   c10::optional<torch::Tensor> doc_start,
+                                                   c10::optional<torch::Tensor> doc_end) {
   const int* kvl = nullptr;
   if (kv_len.has_value()) {
     TORCH_CHECK(kv_len->scalar_type() == torch::kInt32 && kv_len->is_cuda() &&
@@ -603,6 +639,9 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
   TORCH_CHECK(win == 0 || Sq == Sk, "flash_fwd: a sliding window needs Sq == Sk");
   const float* relb =
       rel_bias_ptr(rel_bias, q, H, Sq, Sk, slopes != nullptr, window, "flash_fwd");
+  const int *docs = nullptr, *doce = nullptr;
+  doc_bounds_ptrs(doc_start, doc_end, q, B, Sq, Sk, causal, slopes != nullptr,
+                  window, relb != nullptr, "flash_fwd", &docs, &doce);
   auto o = torch::empty({B, Sq, H, D}, q.options());
   auto lse = torch::empty({B, H, Sq}, q.options().dtype(torch::kFloat32));
   flash_fwd_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
@@ -610,7 +649,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
                  k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1),
                  v.stride(2), o.stride(0), o.stride(1), o.stride(2), B, H, Sq, Sk, D,
                  (float)scale, (float)p_drop, (uint64_t)seed, causal ? 1 : 0,
-                 kv_group, slopes, win, relb, cur_stream());
+                 kv_group, slopes, win, relb, docs, cur_stream());
   check_launch("flash_fwd");
   return {o, lse};
 }
@@ -623,7 +662,8 @@ py::tuple flash_bwd(
     bool causal, c10::optional<torch::Tensor> dqkv,
     c10::optional<torch::Tensor> kv_len,
     c10::optional<torch::Tensor> alibi_slopes, int64_t window,
-    c10::optional<torch::Tensor> rel_bias) {
+    c10::optional<torch::Tensor> rel_bias, c10::optional<torch::Tensor> doc_start,
+    c10::optional<torch::Tensor> doc_end) {
   const int* kvl = nullptr;
   if (kv_len.has_value()) {
     TORCH_CHECK(kv_len->scalar_type() == torch::kInt32 && kv_len->is_cuda() &&
@@ -640,6 +680,9 @@ py::tuple flash_bwd(
   TORCH_CHECK(win == 0 || Sq == Sk, "flash_bwd: a sliding window needs Sq == Sk");
   const float* relb =
       rel_bias_ptr(rel_bias, q, H, Sq, Sk, slopes != nullptr, window, "flash_bwd");
+  const int *docs = nullptr, *doce = nullptr;
+  doc_bounds_ptrs(doc_start, doc_end, q, B, Sq, Sk, causal, slopes != nullptr,
+                  window, relb != nullptr, "flash_bwd", &docs, &doce);
   // the dQ kernel accumulates into it with atomics: zero-filled here
   torch::Tensor d_relb;
   if (relb != nullptr) d_relb = torch::zeros_like(rel_bias.value());
@@ -667,7 +710,8 @@ py::tuple flash_bwd(
       dq.stride(1), dq.stride(2), dk.stride(0), dk.stride(1), dk.stride(2),
       dv.stride(0), dv.stride(1), dv.stride(2), B, H, Sq, Sk, D, (float)scale,
       (float)p_drop, (uint64_t)seed, causal ? 1 : 0, kv_group, slopes, win, relb,
-      relb != nullptr ? d_relb.data_ptr<float>() : nullptr, cur_stream());
+      relb != nullptr ? d_relb.data_ptr<float>() : nullptr, docs, doce,
+      cur_stream());
   check_launch("flash_bwd");
   if (relb != nullptr) return py::make_tuple(dq, dk, dv, d_relb);
   return py::make_tuple(dq, dk, dv);
@@ -687,9 +731,22 @@ void attn_dropout_apply(torch::Tensor x, int64_t Sq, int64_t Sk, double p,
 // RoPE / SwiGLU
 // ---------------------------------------------------------------------------
 torch::Tensor rope(torch::Tensor x, torch::Tensor cos_t, torch::Tensor sin_t,
-                   int64_t pos0, bool bwd) {
+                   int64_t pos0, bool bwd, c10::optional<torch::Tensor> pos_ids) {
   // x: [B, S, NH, HS] (strided view ok, last dim contiguous)
   TORCH_CHECK(x.dim() == 4 && x.stride(3) == 1);
+  // optional per-token table rows (packed documents): int32 [B, S]; the kernel
+  // clamps them into the table
+  const int* pid = nullptr;
+  if (pos_ids.has_value()) {
+    TORCH_CHECK(pos_ids->scalar_type() == torch::kInt32 && pos_ids->is_cuda() &&
+                    pos_ids->get_device() == x.get_device() &&
+                    pos_ids->is_contiguous() && pos_ids->dim() == 2 &&
+                    pos_ids->size(0) == x.size(0) && pos_ids->size(1) == x.size(1),
+                "rope: pos_ids must be a contiguous int32 tensor of shape [B, S] "
+                "on x's device");
+    TORCH_CHECK(cos_t.size(0) > 0 && sin_t.size(0) == cos_t.size(0));
+    pid = pos_ids->data_ptr<int>();
+  }
   auto out = torch::empty(x.sizes(), x.options());
   const int B = (int)x.size(0), S = (int)x.size(1), NH = (int)x.size(2),
             HS = (int)x.size(3);
@@ -697,7 +754,7 @@ torch::Tensor rope(torch::Tensor x, torch::Tensor cos_t, torch::Tensor sin_t,
                 : (is_bf16(x) ? rope_fwd_bf16 : rope_fwd_f32);
   fn(x.data_ptr(), out.data_ptr(), cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
      x.stride(0), x.stride(1), x.stride(2), out.stride(0), out.stride(1),
-     out.stride(2), B, S, NH, HS, (int)pos0, cur_stream());
+     out.stride(2), B, S, NH, HS, (int)pos0, pid, (int)cos_t.size(0), cur_stream());
   check_launch("rope");
   return out;
 }
@@ -843,16 +900,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_fwd", &flash_fwd, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("scale"), py::arg("p_drop"), py::arg("seed"), py::arg("causal"),
         py::arg("kv_len"), py::arg("alibi_slopes") = py::none(), py::arg("window") = 0,
-        py::arg("rel_bias") = py::none());
+        py::arg("rel_bias") = py::none(), py::arg("doc_start") = py::none(),
+        py::arg("doc_end") = py::none());
   m.def("flash_bwd", &flash_bwd, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o"), py::arg("dout"), py::arg("lse"), py::arg("scale"),
         py::arg("p_drop"), py::arg("seed"), py::arg("causal"), py::arg("dqkv"),
         py::arg("kv_len"), py::arg("alibi_slopes") = py::none(), py::arg("window") = 0,
-        py::arg("rel_bias") = py::none());
+        py::arg("rel_bias") = py::none(), py::arg("doc_start") = py::none(),
+        py::arg("doc_end") = py::none());
   m.def("attn_dropout_apply", &attn_dropout_apply);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);
-  m.def("rope", &rope);
+  m.def("rope", &rope, py::arg("x"), py::arg("cos_t"), py::arg("sin_t"),
+        py::arg("pos0"), py::arg("bwd"), py::arg("pos_ids") = py::none());
   m.def("rope_kv_insert", &rope_kv_insert);
   m.def("quant_fp8", &quant_fp8);
   m.def("res_norm_fwd", &res_norm_fwd);

@@ -32,7 +32,8 @@
 // readfirstlane), into
 //   interior: every (q, kv) pair visible -- all q rows < Sq, all kv rows <
 //             sk_eff, under `causal` lowest q >= highest kv, under WINDOW the
-//             farthest pair inside the band;
+//             farthest pair inside the band, under DOCS all keys inside the
+//             document of every query;
 //   edge:     everything else (diagonal, ragged, padded, band border).
 // One generic lambda per kernel, instantiated on `MASKED`, gives both bodies.
 // The interior body has no validity compares, selects or sentinel guards; the
@@ -252,6 +253,29 @@ __device__ __forceinline__ int block_tile() {
 // themselves are in range for every lane, padded rows included).  bwd_q also
 // reduces the bias gradient (see there).  The RELB=false instantiations never
 // touch the pointers.
+// DOCS: compile-time variant for packed samples (Megatron's
+// reset_attention_mask, flash-attn's varlen): causal attention with Sq == Sk
+// that stays inside the query's own document.  doc_start / doc_end are int32
+// [B, S]: the first token of, and one past the last token of, the document
+// that holds token i.  Query i sees key j iff doc_start[i] <= j <= i, which
+// for contiguous documents equals j <= i < doc_end[j].  A lane of the forward
+// and of bwd_q owns one query and carries the lower bound, a lane of bwd_kv
+// owns one key and carries the upper bound.  Both tables are monotone along
+// the sequence, so the tile skips and the tile class of WINDOW carry over
+// with other scalars.  Every value read is clamped (lower bound into [0, q],
+// upper bound into [kv + 1, Sq]): a malformed table gives wrong numbers, never
+// an out-of-range loop or a barrier that part of a workgroup skips.  The
+// DOCS=false instantiations never touch the pointers.
+__device__ __forceinline__ int doc_lo_load(const int* __restrict__ row, int i,
+                                           int S) {
+  return min(max(row[min(i, S - 1)], 0), i);
+}
+
+__device__ __forceinline__ int doc_hi_load(const int* __restrict__ row, int i,
+                                           int S) {
+  return min(max(row[min(i, S - 1)], i + 1), S);
+}
+
 #define RELB_LOG2E 1.4426950408889634f
 
 // global diagonal index -> staged value; out-of-table diagonals (only padded
@@ -283,7 +307,7 @@ __device__ __forceinline__ void relb_flush(float* ring, float* __restrict__ grow
   }
 }
 
-template <int D, bool ALIBI, bool WINDOW, bool RELB>
+template <int D, bool ALIBI, bool WINDOW, bool RELB, bool DOCS>
 __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, bf16_t* __restrict__ o, float* __restrict__ lse,
@@ -292,7 +316,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     int64_t v_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh, int H, int Sq, int Sk,
     float scale, float p_drop, uint64_t seed, int causal, int kv_group,
     const float* __restrict__ alibi_slopes, int window,
-    const float* __restrict__ rel_bias) {
+    const float* __restrict__ rel_bias, const int* __restrict__ doc_start) {
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
 
@@ -360,6 +384,19 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
   // key any query of this block can see (uniform across the workgroup)
   int round0 = 0;
   if constexpr (WINDOW) round0 = max(0, q_block - window + 1) / (2 * KVB);
+  // packed documents: lane's lower bound; the block's lowest bound (its first
+  // query's: doc_start is non-decreasing) picks the first staging round, the
+  // wave's first and last queries give the sub-tile skip and the tile class
+  int doc_lo = 0, doc_lo_w = 0, doc_lo_top = 0;
+  if constexpr (DOCS) {
+    const int* dsp = doc_start + (int64_t)b * Sq;
+    doc_lo = doc_lo_load(dsp, qg, Sq);
+    round0 = __builtin_amdgcn_readfirstlane(doc_lo_load(dsp, q_block, Sq)) /
+             (2 * KVB);
+    doc_lo_w = __builtin_amdgcn_readfirstlane(doc_lo_load(dsp, q_base, Sq));
+    doc_lo_top =
+        __builtin_amdgcn_readfirstlane(doc_lo_load(dsp, q_base + QB - 1, Sq));
+  }
   const int n_diag = Sq + Sk - 1;
   const float* rbp = nullptr;
   if constexpr (RELB) rbp = rel_bias + (int64_t)h * n_diag;
@@ -386,6 +423,9 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     if constexpr (WINDOW) {  // sub-tile entirely below this wave's band
       if (kv0 + KVB - 1 < q_base - window + 1) continue;
     }
+    if constexpr (DOCS) {  // sub-tile entirely before this wave's documents
+      if (kv0 + KVB - 1 < doc_lo_w) continue;
+    }
 
     // S = K x Q^T : two 32x32 tiles
     f32x16_t s0{}, s1{};
@@ -408,6 +448,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     bool interior = kv0 + KVB <= sk_eff && q_base + QB <= Sq &&
                     (!causal || q_base >= kv0 + KVB - 1);
     if constexpr (WINDOW) interior = interior && (q_base + QB - 1 - kv0 < window);
+    if constexpr (DOCS) interior = interior && (kv0 >= doc_lo_top);
     auto softmax_tile = [&](auto masked_c) {
       constexpr bool MASKED = decltype(masked_c)::value;
       float pmax = -3.0e38f;
@@ -436,6 +477,10 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
           if constexpr (WINDOW) {
             if (qg - kva >= window) a = -3.0e38f;
             if (qg - kvb >= window) bb = -3.0e38f;
+          }
+          if constexpr (DOCS) {
+            if (kva < doc_lo) a = -3.0e38f;
+            if (kvb < doc_lo) bb = -3.0e38f;
           }
         }
         sv[0][r] = a;
@@ -581,7 +626,7 @@ __global__ void rowdot_kernel(const bf16_t* __restrict__ dout,
 // restarts per GQA query head; all its conditions are workgroup-uniform.  The
 // staged values, the compute body and their order are those of the plain
 // loop, so dK and dV do not change by a bit.
-template <int D, bool ALIBI, bool WINDOW, bool RELB>
+template <int D, bool ALIBI, bool WINDOW, bool RELB, bool DOCS>
 __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
@@ -593,7 +638,8 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
     int64_t dk_sb, int64_t dk_ss, int64_t dk_sh, int64_t dv_sb, int64_t dv_ss,
     int64_t dv_sh, int H, int Sq, int Sk, float scale, float p_drop, uint64_t seed,
     int causal, int kv_group, const float* __restrict__ alibi_slopes,
-    int window, const float* __restrict__ rel_bias) {
+    int window, const float* __restrict__ rel_bias,
+    const int* __restrict__ doc_end) {
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
   // D=64: 64-row staging tiles.  D=128: 32-row tiles.
@@ -682,6 +728,19 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
   // the sequence length, so the sum cannot overflow)
   int q_hi = Sq;
   if constexpr (WINDOW) q_hi = min(Sq, kv_block + QBLK + window - 1);
+  // packed documents: lane's upper bound; the block's highest bound (its last
+  // valid key's: doc_end is non-decreasing) ends the q-tile loop for the whole
+  // workgroup, the wave's last and first keys give the skip and the tile class
+  int doc_hi = 0, doc_hi_w = 0, doc_hi_bot = 0;
+  if constexpr (DOCS) {
+    const int* dep = doc_end + (int64_t)b * Sk;
+    doc_hi = doc_hi_load(dep, kvg, Sk);
+    const int k_last = max(min(kv_block + QBLK, min(Sk, sk_eff)) - 1, 0);
+    q_hi = min(Sq, __builtin_amdgcn_readfirstlane(doc_hi_load(dep, k_last, Sk)));
+    doc_hi_w =
+        __builtin_amdgcn_readfirstlane(doc_hi_load(dep, kv_base + QB - 1, Sk));
+    doc_hi_bot = __builtin_amdgcn_readfirstlane(doc_hi_load(dep, kv_base, Sk));
+  }
   const int n_qtiles = (kv_block < sk_eff) ? CDIV(q_hi, QTILE) : 0;
 
   // Dropout key of element (q, kv4), first mixer word, mod 2^32:
@@ -793,6 +852,9 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
     if constexpr (WINDOW) {  // entirely below this wave's band
       if (q0 - (kv_base + QB - 1) >= window) return;
     }
+    if constexpr (DOCS) {  // entirely behind this wave's documents
+      if (q0 >= doc_hi_w) return;
+    }
 
     // rolled: one copy of the four element bodies, and no per-sub-tile set of
     // hoisted addresses (unrolled, D=64 took 254 VGPRs instead of 188)
@@ -802,6 +864,9 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
       if (causal && q0s + QB - 1 < kv_base) continue;
       if constexpr (WINDOW) {
         if (q0s - (kv_base + QB - 1) >= window) continue;
+      }
+      if constexpr (DOCS) {
+        if (q0s >= doc_hi_w) continue;
       }
       const int ro = sub * QB;  // row offset inside the staged images
 
@@ -824,6 +889,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
                       (!causal || q0s >= kv_base + QB - 1);
       if constexpr (WINDOW)
         interior = interior && (q0s + QB - 1 - kv_base < window);
+      if constexpr (DOCS) interior = interior && (q0s + QB - 1 < doc_hi_bot);
 
       // per-chunk: compute Pd/dS for 8 regs, repack, feed the MFMAs (short
       // lifetimes).  The element body is instantiated on MASKED (tile class)
@@ -889,6 +955,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
               bool valid =
                   qrow < Sq && kvg < sk_eff && (!causal || qrow >= kvg);
               if constexpr (WINDOW) valid = valid && (qrow - kvg < window);
+              if constexpr (DOCS) valid = valid && (qrow < doc_hi);
               const uint32_t vm = valid ? 0xFFFFFFFFu : 0u;
               const float p = and_f32(__expf(x), vm);
               pd8[k] = p * keep;
@@ -992,7 +1059,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
 // of the next staging round, between the two barriers the loop already has,
 // and the rest behind the loop: one global fp32 atomic per (workgroup,
 // touched diagonal), whatever the sequence length.
-template <int D, bool ALIBI, bool WINDOW, bool RELB>
+template <int D, bool ALIBI, bool WINDOW, bool RELB, bool DOCS>
 __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
@@ -1004,7 +1071,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
     int64_t dq_sh, int H, int Sq, int Sk, float scale, float p_drop, uint64_t seed,
     int causal, int kv_group, const float* __restrict__ alibi_slopes,
     int window, const float* __restrict__ rel_bias,
-    float* __restrict__ d_rel_bias) {
+    float* __restrict__ d_rel_bias, const int* __restrict__ doc_start) {
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
   constexpr int KVTILE = (D == 64) ? 2 * QB : QB;
@@ -1068,6 +1135,16 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
   // sliding window: start at the tile holding the block's lowest visible key
   int tile0 = 0;
   if constexpr (WINDOW) tile0 = max(0, q_block - window + 1) / KVTILE;
+  // packed documents: as in the forward
+  int doc_lo = 0, doc_lo_w = 0, doc_lo_top = 0;
+  if constexpr (DOCS) {
+    const int* dsp = doc_start + (int64_t)b * Sq;
+    doc_lo = doc_lo_load(dsp, qg, Sq);
+    tile0 = __builtin_amdgcn_readfirstlane(doc_lo_load(dsp, q_block, Sq)) / KVTILE;
+    doc_lo_w = __builtin_amdgcn_readfirstlane(doc_lo_load(dsp, q_base, Sq));
+    doc_lo_top =
+        __builtin_amdgcn_readfirstlane(doc_lo_load(dsp, q_base + QB - 1, Sq));
+  }
 
   const int n_diag = Sq + Sk - 1;
   const float* rbp = nullptr;
@@ -1104,6 +1181,9 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
       if constexpr (WINDOW) {  // sub-tile entirely below this wave's band
         if (kv0s + QB - 1 < q_base - window + 1) continue;
       }
+      if constexpr (DOCS) {  // sub-tile entirely before this wave's documents
+        if (kv0s + QB - 1 < doc_lo_w) continue;
+      }
       const int ro = sub * QB;
 
       // S^T[kv][q] = K x Q^T ;  dPd^T[kv][q] = V x dO^T   (lane col = q)
@@ -1125,6 +1205,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
                       (!causal || q_base >= kv0s + QB - 1);
       if constexpr (WINDOW)
         interior = interior && (q_base + QB - 1 - kv0s < window);
+      if constexpr (DOCS) interior = interior && (kv0s >= doc_lo_top);
       auto ds_tile = [&](auto masked_c) {
         constexpr bool MASKED = decltype(masked_c)::value;
         const uint32_t thr8 = drop_threshold_u8(p_drop);
@@ -1182,6 +1263,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
             if constexpr (MASKED) {
               bool valid = kv < sk_eff && qg < Sq && (!causal || kv <= qg);
               if constexpr (WINDOW) valid = valid && (qg - kv < window);
+              if constexpr (DOCS) valid = valid && (kv >= doc_lo);
               const uint32_t vm = valid ? 0xFFFFFFFFu : 0u;
               float p = and_f32(__expf(x), vm);
               float keep = (p_drop > 0.f) ? drop_keep_byte(h, j, thr8, ks) : 1.f;
@@ -1276,36 +1358,52 @@ extern "C" void flash_fwd_bf16(const void* q, const void* k, const void* v, void
                                float scale, float p_drop, uint64_t seed, int causal,
                                int kv_group, const float* alibi_slopes,
                                int window, const float* rel_bias,
-                               hipStream_t stream) {
+                               const int* doc_start, hipStream_t stream) {
   dim3 grid(CDIV(Sq, QBLK), B * H);
   dim3 block(256);
 #define FWD_ARGS                                                                     \
   (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, kv_len,     \
       q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, o_sb, o_ss, o_sh, H, Sq, \
-      Sk, scale, p_drop, seed, causal, kv_group, alibi_slopes, window, rel_bias
-  // the binding rejects window, ALiBi and a relative-position table in any
-  // combination: no cross product
+      Sk, scale, p_drop, seed, causal, kv_group, alibi_slopes, window, rel_bias,     \
+      doc_start
+  // the binding rejects window, ALiBi, a relative-position table and packed
+  // documents in any combination: no cross product
+  const bool docs = doc_start != nullptr;
   const bool alibi = alibi_slopes != nullptr;
   const bool relb = rel_bias != nullptr;
   window = window > 0 ? min(window, max(Sq, Sk)) : 0;  // same mask, no overflow
   if (D == 64) {
     if (alibi)
-      flash_fwd_kernel<64, true, false, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<64, true, false, false, false>
+          <<<grid, block, 0, stream>>>(FWD_ARGS);
     else if (window > 0)
-      flash_fwd_kernel<64, false, true, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<64, false, true, false, false>
+          <<<grid, block, 0, stream>>>(FWD_ARGS);
     else if (relb)
-      flash_fwd_kernel<64, false, false, true><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<64, false, false, true, false>
+          <<<grid, block, 0, stream>>>(FWD_ARGS);
+    else if (docs)
+      flash_fwd_kernel<64, false, false, false, true>
+          <<<grid, block, 0, stream>>>(FWD_ARGS);
     else
-      flash_fwd_kernel<64, false, false, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<64, false, false, false, false>
+          <<<grid, block, 0, stream>>>(FWD_ARGS);
   } else if (D == 128) {
     if (alibi)
-      flash_fwd_kernel<128, true, false, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<128, true, false, false, false>
+          <<<grid, block, 0, stream>>>(FWD_ARGS);
     else if (window > 0)
-      flash_fwd_kernel<128, false, true, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<128, false, true, false, false>
+          <<<grid, block, 0, stream>>>(FWD_ARGS);
     else if (relb)
-      flash_fwd_kernel<128, false, false, true><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<128, false, false, true, false>
+          <<<grid, block, 0, stream>>>(FWD_ARGS);
+    else if (docs)
+      flash_fwd_kernel<128, false, false, false, true>
+          <<<grid, block, 0, stream>>>(FWD_ARGS);
     else
-      flash_fwd_kernel<128, false, false, false><<<grid, block, 0, stream>>>(FWD_ARGS);
+      flash_fwd_kernel<128, false, false, false, false>
+          <<<grid, block, 0, stream>>>(FWD_ARGS);
   }
 #undef FWD_ARGS
 }
@@ -1321,7 +1419,8 @@ extern "C" void flash_bwd_bf16(
     int64_t dv_sb, int64_t dv_ss, int64_t dv_sh, int B, int H, int Sq, int Sk, int D,
     float scale, float p_drop, uint64_t seed, int causal, int kv_group,
     const float* alibi_slopes, int window, const float* rel_bias,
-    float* d_rel_bias, hipStream_t stream) {
+    float* d_rel_bias, const int* doc_start, const int* doc_end,
+    hipStream_t stream) {
   // Drow = rowsum(dO * O)  (dO and O share layout; use dO's strides for both:
   // the wrapper guarantees o was allocated with the same layout)
   {
@@ -1343,34 +1442,38 @@ extern "C" void flash_bwd_bf16(
       drow_ws, kv_len, (bf16_t*)dk, (bf16_t*)dv, q_sb, q_ss, q_sh, k_sb, k_ss,       \
       k_sh, v_sb, v_ss, v_sh, do_sb, do_ss, do_sh, dk_sb, dk_ss, dk_sh, dv_sb,       \
       dv_ss, dv_sh, H, Sq, Sk, scale, p_drop, seed, causal, kv_group,                \
-      alibi_slopes, window, rel_bias
+      alibi_slopes, window, rel_bias, doc_end
 #define BWD_ARGS_Q                                                                   \
   (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse,    \
       drow_ws, kv_len, (bf16_t*)dq, q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss,  \
       v_sh, do_sb, do_ss, do_sh, dq_sb, dq_ss, dq_sh, H, Sq, Sk, scale, p_drop,      \
-      seed, causal, kv_group, alibi_slopes, window, rel_bias, d_rel_bias
+      seed, causal, kv_group, alibi_slopes, window, rel_bias, d_rel_bias, doc_start
   dim3 block(256);
   const int Hkv = H / kv_group;  // bwd_kv grid spans the KV heads
   const dim3 grid_kv(CDIV(Sk, QBLK), B * Hkv), grid_q(CDIV(Sq, QBLK), B * H);
-#define BWD_LAUNCH(DD, AL, WIN, RB)                                                  \
+#define BWD_LAUNCH(DD, AL, WIN, RB, DOC)                                             \
   do {                                                                               \
-    flash_bwd_kv_kernel<DD, AL, WIN, RB>                                             \
+    flash_bwd_kv_kernel<DD, AL, WIN, RB, DOC>                                        \
         <<<grid_kv, block, 0, stream>>>(BWD_ARGS_KV);                                \
-    flash_bwd_q_kernel<DD, AL, WIN, RB><<<grid_q, block, 0, stream>>>(BWD_ARGS_Q);   \
+    flash_bwd_q_kernel<DD, AL, WIN, RB, DOC>                                         \
+        <<<grid_q, block, 0, stream>>>(BWD_ARGS_Q);                                  \
   } while (0)
   const bool alibi = alibi_slopes != nullptr;
   const bool relb = rel_bias != nullptr;
+  const bool docs = doc_start != nullptr;
   window = window > 0 ? min(window, max(Sq, Sk)) : 0;  // same mask, no overflow
   if (D == 64) {
-    if (alibi) BWD_LAUNCH(64, true, false, false);
-    else if (window > 0) BWD_LAUNCH(64, false, true, false);
-    else if (relb) BWD_LAUNCH(64, false, false, true);
-    else BWD_LAUNCH(64, false, false, false);
+    if (alibi) BWD_LAUNCH(64, true, false, false, false);
+    else if (window > 0) BWD_LAUNCH(64, false, true, false, false);
+    else if (relb) BWD_LAUNCH(64, false, false, true, false);
+    else if (docs) BWD_LAUNCH(64, false, false, false, true);
+    else BWD_LAUNCH(64, false, false, false, false);
   } else if (D == 128) {
-    if (alibi) BWD_LAUNCH(128, true, false, false);
-    else if (window > 0) BWD_LAUNCH(128, false, true, false);
-    else if (relb) BWD_LAUNCH(128, false, false, true);
-    else BWD_LAUNCH(128, false, false, false);
+    if (alibi) BWD_LAUNCH(128, true, false, false, false);
+    else if (window > 0) BWD_LAUNCH(128, false, true, false, false);
+    else if (relb) BWD_LAUNCH(128, false, false, true, false);
+    else if (docs) BWD_LAUNCH(128, false, false, false, true);
+    else BWD_LAUNCH(128, false, false, false, false);
   }
 #undef BWD_LAUNCH
 }

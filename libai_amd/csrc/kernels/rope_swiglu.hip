@@ -18,14 +18,19 @@ namespace {
 // RoPE: x[..., :hs/2], x[..., hs/2:] rotated pairwise with cos/sin[s, hs/2]
 // half-split convention (HF Llama rotate_half):
 //   out1 = x1*cos - x2*sin ;  out2 = x2*cos + x1*sin
+// POS: the table row of token (b, s) is pos_ids[b*S + s] (int32 [B, S]; in a
+// packed sample every document restarts at 0), clamped into the table's n_pos
+// rows, instead of pos0 + s.  The POS=false instantiations never touch the
+// pointer.
 // ---------------------------------------------------------------------------
-template <class E, bool BWD>
+template <class E, bool BWD, bool POS>
 __global__ void rope_kernel(const typename E::T* __restrict__ x,
                             typename E::T* __restrict__ out,
                             const float* __restrict__ cos_t,
                             const float* __restrict__ sin_t, int64_t sb, int64_t ss,
                             int64_t sh, int64_t ob, int64_t os, int64_t oh, int B,
-                            int S, int NH, int HS, int pos0) {
+                            int S, int NH, int HS, int pos0,
+                            const int* __restrict__ pos_ids, int n_pos) {
   // one thread: VEC elems of x1 + matching VEC of x2
   constexpr int V = E::VEC;
   const int half = HS / 2;
@@ -40,8 +45,10 @@ __global__ void rope_kernel(const typename E::T* __restrict__ x,
     const int b = (int)(t / S);
     const typename E::T* xp = x + b * sb + (int64_t)s * ss + h * sh;
     typename E::T* op = out + b * ob + (int64_t)s * os + h * oh;
-    const float* cp = cos_t + (int64_t)(pos0 + s) * half + c * V;
-    const float* sp = sin_t + (int64_t)(pos0 + s) * half + c * V;
+    int row = pos0 + s;
+    if constexpr (POS) row = min(max(pos_ids[(int64_t)b * S + s], 0), n_pos - 1);
+    const float* cp = cos_t + (int64_t)row * half + c * V;
+    const float* sp = sin_t + (int64_t)row * half + c * V;
     using VecT = typename E::VecT;
     VecT x1 = *(const VecT*)(xp + c * V);
     VecT x2 = *(const VecT*)(xp + half + c * V);
@@ -183,21 +190,35 @@ inline int64_t grid_for(int64_t n) {
                                   const float* sin_t, int64_t sb, int64_t ss,          \
                                   int64_t sh, int64_t ob, int64_t os, int64_t oh,      \
                                   int B, int S, int NH, int HS, int pos0,              \
+                                  const int* pos_ids, int n_pos,                       \
                                   hipStream_t stream) {                                \
     int64_t n = (int64_t)B * S * NH * (HS / 2 / ETYPE::VEC);                           \
-    rope_kernel<ETYPE, false><<<dim3((uint32_t)grid_for(n)), 256, 0, stream>>>(        \
-        (const ETYPE::T*)x, (ETYPE::T*)out, cos_t, sin_t, sb, ss, sh, ob, os, oh, B,   \
-        S, NH, HS, pos0);                                                              \
+    const dim3 grid((uint32_t)grid_for(n));                                            \
+    if (pos_ids != nullptr)                                                            \
+      rope_kernel<ETYPE, false, true><<<grid, 256, 0, stream>>>(                       \
+          (const ETYPE::T*)x, (ETYPE::T*)out, cos_t, sin_t, sb, ss, sh, ob, os, oh,    \
+          B, S, NH, HS, pos0, pos_ids, n_pos);                                         \
+    else                                                                               \
+      rope_kernel<ETYPE, false, false><<<grid, 256, 0, stream>>>(                      \
+          (const ETYPE::T*)x, (ETYPE::T*)out, cos_t, sin_t, sb, ss, sh, ob, os, oh,    \
+          B, S, NH, HS, pos0, pos_ids, n_pos);                                         \
   }                                                                                    \
   extern "C" void rope_bwd_##SUFF(const void* dy, void* dx, const float* cos_t,        \
                                   const float* sin_t, int64_t sb, int64_t ss,          \
                                   int64_t sh, int64_t ob, int64_t os, int64_t oh,      \
                                   int B, int S, int NH, int HS, int pos0,              \
+                                  const int* pos_ids, int n_pos,                       \
                                   hipStream_t stream) {                                \
     int64_t n = (int64_t)B * S * NH * (HS / 2 / ETYPE::VEC);                           \
-    rope_kernel<ETYPE, true><<<dim3((uint32_t)grid_for(n)), 256, 0, stream>>>(         \
-        (const ETYPE::T*)dy, (ETYPE::T*)dx, cos_t, sin_t, sb, ss, sh, ob, os, oh, B,   \
-        S, NH, HS, pos0);                                                              \
+    const dim3 grid((uint32_t)grid_for(n));                                            \
+    if (pos_ids != nullptr)                                                            \
+      rope_kernel<ETYPE, true, true><<<grid, 256, 0, stream>>>(                        \
+          (const ETYPE::T*)dy, (ETYPE::T*)dx, cos_t, sin_t, sb, ss, sh, ob, os, oh,    \
+          B, S, NH, HS, pos0, pos_ids, n_pos);                                         \
+    else                                                                               \
+      rope_kernel<ETYPE, true, false><<<grid, 256, 0, stream>>>(                       \
+          (const ETYPE::T*)dy, (ETYPE::T*)dx, cos_t, sin_t, sb, ss, sh, ob, os, oh,    \
+          B, S, NH, HS, pos0, pos_ids, n_pos);                                         \
   }                                                                                    \
   extern "C" void swiglu_fwd_##SUFF(const void* x, void* y, int64_t rows, int F,       \
                                     hipStream_t stream) {                              \

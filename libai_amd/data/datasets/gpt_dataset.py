@@ -3,6 +3,14 @@
 Reference behavior: libai/data/datasets/gpt_dataset.py:101-245 — doc/sample/
 shuffle index triple built by the C++ helpers (libai_amd/_data_helpers.so;
 numpy fallback), np-memmap cached on disk, resumable by index.
+
+``reset_attention_mask=True`` (Megatron's flag of that name, together with its
+``reset_position_ids``): a sample is several documents in one row, and the
+Instance then also carries ``doc_start`` / ``doc_end`` (int32 [s], see
+``libai_amd.data.packing``), taken from the pieces the sample is concatenated
+from -- no EOD token needed.  The label of each document's last token is set
+to -100 (ignored by the loss): its target would be the next document's first
+token.
 """
 
 import hashlib
@@ -12,6 +20,7 @@ import os
 import numpy as np
 import torch
 
+from ..packing import doc_bounds_from_lengths
 from ..structures import DistTensorData, Instance
 
 logger = logging.getLogger(__name__)
@@ -54,8 +63,10 @@ def _build_sample_idx_np(sizes, doc_idx, seq_length, num_epochs, tokens_per_epoc
 
 class GPT2Dataset(torch.utils.data.Dataset):
     def __init__(self, name, indexed_dataset, documents=None, num_samples=None,
-                 max_seq_length=1024, seed=1234, data_prefix=None):
+                 max_seq_length=1024, seed=1234, data_prefix=None,
+                 reset_attention_mask=False):
         self.name = name
+        self.reset_attention_mask = reset_attention_mask
         self.ds = indexed_dataset
         self.seq_length = max_seq_length
         self.seed = seed
@@ -99,17 +110,43 @@ class GPT2Dataset(torch.utils.data.Dataset):
         d1, o1 = self.sample_idx[idx + 1]
         if d0 == d1:
             toks = self.ds.get(self.doc_idx[d0], offset=o0, length=o1 - o0 + 1)
+            part_lens = [len(toks)]
         else:
             parts = [self.ds.get(self.doc_idx[d0], offset=o0)]
             for d in range(d0 + 1, d1):
                 parts.append(self.ds.get(self.doc_idx[d]))
             parts.append(self.ds.get(self.doc_idx[d1], length=o1 + 1))
             toks = np.concatenate(parts)
+            part_lens = [len(p) for p in parts]
         toks = np.asarray(toks[: self.seq_length + 1], dtype=np.int64)
         if len(toks) < self.seq_length + 1:  # tail padding (rare)
             toks = np.pad(toks, (0, self.seq_length + 1 - len(toks)))
         t = torch.from_numpy(toks.copy())
+        if self.reset_attention_mask:
+            return self._packed_instance(t, part_lens)
         return Instance(
             input_ids=DistTensorData(t[:-1]),
             labels=DistTensorData(t[1:], placement_idx=-1),
+        )
+
+    def _packed_instance(self, t, part_lens):
+        """t: the sample's seq_length + 1 tokens; part_lens: token counts of
+        the document pieces it was concatenated from."""
+        s = self.seq_length
+        # piece ends in the seq_length + 1 token stream
+        ends = np.minimum(np.cumsum(np.asarray(part_lens, dtype=np.int64)), s + 1)
+        labels = t[1:].clone()
+        # token e - 1 ends a piece and token e starts the next one
+        cut = ends[(ends >= 1) & (ends <= s)]
+        labels[torch.from_numpy(cut - 1)] = -100
+        # the inputs are tokens [0, s): clip the pieces to the row
+        in_ends = np.unique(np.minimum(ends, s))
+        in_ends = in_ends[in_ends > 0]
+        lengths = np.diff(np.concatenate([[0], in_ends]))
+        doc_start, doc_end, _ = doc_bounds_from_lengths(lengths, s)
+        return Instance(
+            input_ids=DistTensorData(t[:-1]),
+            labels=DistTensorData(labels, placement_idx=-1),
+            doc_start=DistTensorData(doc_start),
+            doc_end=DistTensorData(doc_end),
         )

@@ -7,6 +7,7 @@ curves are reproducible across ranks and resumes.
 
 import torch
 
+from ..packing import doc_bounds_from_lengths
 from ..structures import DistTensorData, Instance
 
 __all__ = ["SyntheticGPTDataset", "SyntheticBertDataset", "SyntheticImageDataset"]
@@ -14,13 +15,34 @@ __all__ = ["SyntheticGPTDataset", "SyntheticBertDataset", "SyntheticImageDataset
 
 class SyntheticGPTDataset(torch.utils.data.Dataset):
     """GPT sample contract (reference: libai/data/datasets/gpt_dataset.py:92-98):
-    Instance(input_ids [s], labels [s] tagged for the last stage)."""
+    Instance(input_ids [s], labels [s] tagged for the last stage).
 
-    def __init__(self, vocab_size=50257, seq_length=1024, size=65536, seed=0):
+    ``packed=True``: every row is a run of documents with seeded random lengths
+    (uniform on [1, 2 * mean_doc_length - 1], the last one cut at the row's
+    end).  The Instance then also carries ``doc_start`` / ``doc_end`` (int32
+    [s], see ``libai_amd.data.packing``) and the label of each document's last
+    token is -100, as ``GPT2Dataset(reset_attention_mask=True)`` produces."""
+
+    def __init__(self, vocab_size=50257, seq_length=1024, size=65536, seed=0,
+                 packed=False, mean_doc_length=128):
+        if packed and mean_doc_length < 1:
+            raise ValueError(f"mean_doc_length must be >= 1, got {mean_doc_length}")
         self.vocab_size = vocab_size
         self.seq_length = seq_length
         self.size = size
         self.seed = seed
+        self.packed = packed
+        self.mean_doc_length = int(mean_doc_length)
+
+    def doc_lengths(self, idx):
+        """The document lengths of (packed) row idx; they sum to seq_length."""
+        g = torch.Generator().manual_seed((self.seed + idx) * 2654435761 % (2**63) + 1)
+        lengths, left = [], self.seq_length
+        while left > 0:
+            n = int(torch.randint(1, 2 * self.mean_doc_length, (1,), generator=g))
+            lengths.append(min(n, left))
+            left -= lengths[-1]
+        return lengths
 
     def __len__(self):
         return self.size
@@ -28,6 +50,17 @@ class SyntheticGPTDataset(torch.utils.data.Dataset):
     def __getitem__(self, idx):
         g = torch.Generator().manual_seed(self.seed + idx)
         tokens = torch.randint(0, self.vocab_size, (self.seq_length + 1,), generator=g)
+        if self.packed:
+            doc_start, doc_end, _ = doc_bounds_from_lengths(self.doc_lengths(idx),
+                                                            self.seq_length)
+            labels = tokens[1:].long().clone()
+            labels[doc_end.long().unique() - 1] = -100
+            return Instance(
+                input_ids=DistTensorData(tokens[:-1].long()),
+                labels=DistTensorData(labels, placement_idx=-1),
+                doc_start=DistTensorData(doc_start),
+                doc_end=DistTensorData(doc_end),
+            )
         return Instance(
             input_ids=DistTensorData(tokens[:-1].long()),
             labels=DistTensorData(tokens[1:].long(), placement_idx=-1),

@@ -33,7 +33,13 @@ class LlamaAttention(nn.Module):
 
     sliding_window=W (Mistral): causal attention over the last W keys, the
     query's own included (HF's ``q_idx - kv_idx < sliding_window``); every
-    branch of forward honours it.  The KV cache keeps all keys."""
+    branch of forward honours it.  The KV cache keeps all keys.
+
+    doc_start / doc_end (int32 [b, s], ``libai_amd.data.packing``): packed
+    documents.  Attention stays causal inside each token's own document and
+    RoPE runs on ``position_ids`` that restart at every document; the flash
+    branch masks in-kernel, the unfused branch builds the same mask.  Training
+    and scoring only: no KV cache, no sliding window."""
 
     def __init__(self, hidden_size, num_heads, max_position_embeddings,
                  init_method, output_init_method, rope_theta=10000.0,
@@ -95,7 +101,22 @@ class LlamaAttention(nn.Module):
         return q, kv[:, :, 0], kv[:, :, 1]
 
     def forward(self, hidden_states, past_key_value=None, use_cache=False,
-                residual=None, static_cache=None, position=None):
+                residual=None, static_cache=None, position=None,
+                doc_start=None, doc_end=None, position_ids=None):
+        if (doc_start is None) != (doc_end is None):
+            raise ValueError("doc_start and doc_end must be given together")
+        if doc_start is not None:
+            if use_cache or past_key_value is not None or static_cache is not None:
+                raise ValueError("packed documents (doc_start / doc_end) cannot "
+                                 "be combined with a KV cache")
+            if self.sliding_window is not None:
+                raise ValueError("packed documents (doc_start / doc_end) cannot "
+                                 "be combined with a sliding window")
+            # int32 contiguous, as the kernels take them (no-ops behind LlamaModel)
+            doc_start = doc_start.to(torch.int32).contiguous()
+            doc_end = doc_end.to(torch.int32).contiguous()
+            if position_ids is None:  # called without LlamaModel
+                position_ids = _doc_position_ids(doc_start)
         if static_cache is not None:
             # hipGraph-capturable decode: RoPE at a device position tensor,
             # in-place KV insert into [b, kvh, MAX, hd] buffers, fused
@@ -126,8 +147,8 @@ class LlamaAttention(nn.Module):
             s = s * du.get_dist_util().tensor_parallel_size
         q, k, v = self._project(hidden_states)
         pos0 = past_key_value[0].shape[2] if past_key_value is not None else 0
-        q = apply_rotary_pos_emb(q, self.max_pos, self.rope_theta, pos0)
-        k = apply_rotary_pos_emb(k, self.max_pos, self.rope_theta, pos0)
+        q = apply_rotary_pos_emb(q, self.max_pos, self.rope_theta, pos0, position_ids)
+        k = apply_rotary_pos_emb(k, self.max_pos, self.rope_theta, pos0, position_ids)
 
         window = self.sliding_window
         if (
@@ -137,8 +158,10 @@ class LlamaAttention(nn.Module):
             and (not use_cache or window is not None)
             and flash_attention_available(self.head_dim, q.dtype, q.device, s, s, None)
         ):
+            doc_bounds = (doc_start, doc_end) if doc_start is not None else None
             o = flash_attention(q, k, v, self.scale, p_drop=0.0, causal=True,
-                                training=self.training, window=window)
+                                training=self.training, window=window,
+                                doc_bounds=doc_bounds)
             context = o.reshape(b, s, self.num_heads_local * self.head_dim)
             if use_cache:  # the cache gets every key, in [b, kvh, s, hd]
                 present = (k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3))
@@ -185,6 +208,11 @@ class LlamaAttention(nn.Module):
                 qi = torch.arange(pos0, pos0 + s, device=q.device)[:, None]
                 kj = torch.arange(sk, device=q.device)[None, :]
                 band = ((qi - kj) >= window)[None].expand(b, s, sk)
+            if doc_start is not None:
+                # [b, s, s] bool, true = masked: key j lies before the first
+                # token of query i's document (on top of the causal mask)
+                kj = torch.arange(s, device=q.device)[None, None, :]
+                band = kj < doc_start[:, :, None]
             probs = fused_scale_mask_softmax(scores, band, scale=self.scale,
                                              causal=causal,
                                              training=self.training)
@@ -200,6 +228,13 @@ class LlamaAttention(nn.Module):
 
         out, _ = self.o_proj(context)
         return out + residual if residual is not None else out
+
+
+def _doc_position_ids(doc_start):
+    """int32 [b, s]: every token's offset inside its own document."""
+    s = doc_start.shape[-1]
+    pos = torch.arange(s, device=doc_start.device, dtype=torch.int32)
+    return (pos - doc_start.to(torch.int32)).contiguous()
 
 
 class LlamaMLP(nn.Module):
@@ -256,8 +291,12 @@ class LlamaDecoderLayer(nn.Module):
                     p.sequence_parallel_grad = True
 
     def forward(self, hidden_states, past_key_value=None, use_cache=False,
-                static_cache=None, position=None):
+                static_cache=None, position=None, doc_start=None, doc_end=None,
+                position_ids=None):
         if static_cache is not None:
+            if doc_start is not None or doc_end is not None:
+                raise ValueError("packed documents (doc_start / doc_end) cannot "
+                                 "be combined with a KV cache")
             # residual + post-attention RMSNorm fused into one kernel
             from ..ops._ext import ext
 
@@ -273,8 +312,15 @@ class LlamaDecoderLayer(nn.Module):
                 ln2 = ln(h)
             return self.mlp(ln2, residual=h)
         ln1 = self.input_layernorm(hidden_states)
+        # the packed-document arguments travel only when given: the plain call
+        # is the one it always was
+        docs = {}
+        if doc_start is not None or doc_end is not None:
+            docs = dict(doc_start=doc_start, doc_end=doc_end,
+                        position_ids=position_ids)
         attn_out = self.self_attn(ln1, past_key_value=past_key_value,
-                                  use_cache=use_cache, residual=hidden_states)
+                                  use_cache=use_cache, residual=hidden_states,
+                                  **docs)
         if use_cache:
             attn_out, present = attn_out
         h = attn_out
@@ -358,13 +404,37 @@ class LlamaModel(nn.Module):
             "sliding_window": cfg.get("sliding_window", None),
         }
 
-    def _run_layer(self, layer, h, past=None, use_cache=False):
+    def _run_layer(self, layer, h, past=None, use_cache=False, doc_start=None,
+                   doc_end=None, position_ids=None):
+        docs = {}  # travel only when given: the plain call stays what it was
+        if doc_start is not None or doc_end is not None:
+            if doc_start is not None and position_ids is None:  # pipeline units
+                position_ids = _doc_position_ids(doc_start)
+            docs = dict(doc_start=doc_start, doc_end=doc_end,
+                        position_ids=position_ids)
         if self.checkpoint_activations and self.training and not use_cache:
-            return act_checkpoint(layer, h, use_reentrant=False)
-        return layer(h, past_key_value=past, use_cache=use_cache)
+            return act_checkpoint(layer, h, use_reentrant=False, **docs)
+        return layer(h, past_key_value=past, use_cache=use_cache, **docs)
 
     def forward(self, input_ids, past_key_values=None, use_cache=False,
-                static_caches=None, position=None):
+                static_caches=None, position=None, doc_start=None, doc_end=None):
+        if (doc_start is None) != (doc_end is None):
+            raise ValueError("doc_start and doc_end must be given together")
+        position_ids = None
+        if doc_start is not None:
+            if use_cache or past_key_values is not None or static_caches is not None:
+                raise ValueError("packed documents (doc_start / doc_end) cannot "
+                                 "be combined with a KV cache")
+            if self.sliding_window is not None:
+                raise ValueError("packed documents (doc_start / doc_end) cannot "
+                                 "be combined with a sliding window")
+            # int32 contiguous, as the kernels take them; positions restart at
+            # every document, computed once per step for all layers
+            doc_start = doc_start.to(device=input_ids.device,
+                                     dtype=torch.int32).contiguous()
+            doc_end = doc_end.to(device=input_ids.device,
+                                 dtype=torch.int32).contiguous()
+            position_ids = _doc_position_ids(doc_start)
         if static_caches is not None:
             h = self.embed_tokens(input_ids)
             for layer, sc in zip(self.layers, static_caches):
@@ -379,7 +449,8 @@ class LlamaModel(nn.Module):
         presents = [] if use_cache else None
         for i, layer in enumerate(self.layers):
             past = past_key_values[i] if past_key_values is not None else None
-            h = self._run_layer(layer, h, past, use_cache)
+            h = self._run_layer(layer, h, past, use_cache, doc_start, doc_end,
+                                position_ids)
             if use_cache:
                 h, p = h
                 presents.append(p)
@@ -447,12 +518,19 @@ class LlamaForCausalLM(nn.Module):
                 else self.lm_head.weight)
 
     def forward(self, input_ids, labels=None, past_key_values=None, use_cache=False,
-                static_caches=None, position=None):
+                static_caches=None, position=None, doc_start=None, doc_end=None):
         if static_caches is not None:
+            if doc_start is not None or doc_end is not None:
+                raise ValueError("packed documents (doc_start / doc_end) cannot "
+                                 "be combined with a KV cache")
             h = self.model(input_ids, static_caches=static_caches,
                            position=position)
             return self.lm_logits(h, self._head_weight())
-        h = self.model(input_ids, past_key_values=past_key_values, use_cache=use_cache)
+        docs = {}
+        if doc_start is not None or doc_end is not None:
+            docs = dict(doc_start=doc_start, doc_end=doc_end)
+        h = self.model(input_ids, past_key_values=past_key_values, use_cache=use_cache,
+                       **docs)
         if use_cache:
             h, presents = h
         logits = self.lm_logits(h, self._head_weight())
@@ -471,6 +549,9 @@ class LlamaForCausalLM(nn.Module):
         keys = {"input_ids"}
         if is_last:
             keys.add("labels")
+        # packed documents: every stage runs attention layers.  The engine
+        # keeps the keys a batch really has
+        keys.update({"doc_start", "doc_end"})
         return keys
 
     def pipeline_units(self):
@@ -478,7 +559,9 @@ class LlamaForCausalLM(nn.Module):
         for i, layer in enumerate(self.model.layers):
             units.append(
                 (i, f"layer_{i}",
-                 (lambda lyr: lambda h, b: self.model._run_layer(lyr, h))(layer))
+                 (lambda lyr: lambda h, b: self.model._run_layer(
+                     lyr, h, doc_start=b.get("doc_start"),
+                     doc_end=b.get("doc_end")))(layer))
             )
 
         def head(h, b):

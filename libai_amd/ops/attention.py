@@ -27,6 +27,16 @@ returns its gradient (dS without the scale, summed along diagonals with fp32
 atomics: summation-order dependent in its last bits, like the embedding
 backward).  Not combinable with ``alibi_slopes`` or ``window``.
 
+Packed documents (Megatron ``reset_attention_mask``, flash-attn varlen): an
+optional ``doc_bounds`` pair ``(doc_start, doc_end)`` of int32 [B, S] tensors
+keeps causal attention inside the query's own document: query i sees key j
+iff doc_start[b, i] <= j <= i.  doc_start[b, i] is the first token of the
+document holding token i, doc_end[b, i] one past its last
+(``libai_amd.data.packing`` builds both).  The kernels mask in-register and
+walk only the tiles on the block diagonal.  Composes with GQA, dropout and
+``kv_len``; not combinable with ``alibi_slopes``, ``window``, ``rel_bias`` or
+``causal=False``, and needs Sq == Sk.
+
 Replaces the reference's K2-K5 chain (reference
 libai/layers/attention.py:211-253).
 """
@@ -73,6 +83,25 @@ def _rel_bias_arg(rel_bias, alibi_slopes, window):
     return rel_bias
 
 
+def _doc_bounds_arg(doc_bounds, causal, alibi_slopes, window, rel_bias):
+    """(doc_start, doc_end) kernel arguments, (None, None) = off.  Rejects
+    document bounds together with anything they do not compose with."""
+    if doc_bounds is None:
+        return None, None
+    if not causal:
+        raise ValueError("doc_bounds requires causal attention")
+    if alibi_slopes is not None:
+        raise ValueError("doc_bounds cannot be combined with alibi_slopes")
+    if window is not None and window != 0:
+        raise ValueError("doc_bounds cannot be combined with a sliding window")
+    if rel_bias is not None:
+        raise ValueError("doc_bounds cannot be combined with rel_bias")
+    doc_start, doc_end = doc_bounds
+    if doc_start is None or doc_end is None:
+        raise ValueError("doc_bounds needs both doc_start and doc_end")
+    return doc_start, doc_end
+
+
 def _window_arg(window, n_keys, causal=True, alibi_slopes=None):
     """Kernel argument for a sliding window: 0 = off.  A window that covers
     all n_keys keys masks nothing and runs the windowless instantiation."""
@@ -109,13 +138,13 @@ class _FlashAttnQKVFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv5, scale, p_drop, causal, kv_len, alibi_slopes=None,
-                window=0, rel_bias=None):
+                window=0, rel_bias=None, doc_start=None, doc_end=None):
         q = qkv5[..., 0, :]
         k = qkv5[..., 1, :]
         v = qkv5[..., 2, :]
         seed = draw_seed() if p_drop > 0 else 0
         o, lse = ext().flash_fwd(q, k, v, scale, p_drop, seed, causal, kv_len,
-                                 alibi_slopes, window, rel_bias)
+                                 alibi_slopes, window, rel_bias, doc_start, doc_end)
         if rel_bias is None:
             ctx.save_for_backward(qkv5, o, lse)
         else:
@@ -124,6 +153,7 @@ class _FlashAttnQKVFn(torch.autograd.Function):
         ctx.kv_len = kv_len
         ctx.alibi_slopes = alibi_slopes  # constant: no grad flows to it
         ctx.window = window
+        ctx.doc_bounds = (doc_start, doc_end)  # int32: no grad flows to them
         ctx.meta = (scale, p_drop, seed, causal)
         return o
 
@@ -136,36 +166,41 @@ class _FlashAttnQKVFn(torch.autograd.Function):
         grads = ext().flash_bwd(
             qkv5[..., 0, :], qkv5[..., 1, :], qkv5[..., 2, :], o, do.contiguous(),
             lse, scale, p_drop, seed, causal, dqkv, ctx.kv_len,
-            ctx.alibi_slopes, ctx.window, rel_bias,
+            ctx.alibi_slopes, ctx.window, rel_bias, *ctx.doc_bounds,
         )
         d_rel = grads[3] if rel_bias is not None and ctx.needs_input_grad[7] else None
-        return dqkv, None, None, None, None, None, None, d_rel
+        return dqkv, None, None, None, None, None, None, d_rel, None, None
 
 
 def flash_attention_qkv(qkv5, scale, p_drop=0.0, causal=True, training=True,
                         kv_len=None, alibi_slopes=None, window=None,
-                        rel_bias=None):
+                        rel_bias=None, doc_bounds=None):
     """qkv5: packed [B, S, H, 3, D] bf16 -> O [B, S, H, D] (zero-copy in/out).
 
     kv_len: optional int32 [B] — keys at/after kv_len[b] are masked out.
     alibi_slopes: optional fp32 [H] — adds slope[h] * (kv - q) to the scores.
     window: optional int W — causal sliding window over the last W keys.
     rel_bias: optional fp32 [H, 2S-1] — adds rel_bias[h, kv - q + S - 1] to the
-    scores; differentiable (not combinable with alibi_slopes or window)."""
+    scores; differentiable (not combinable with alibi_slopes or window).
+    doc_bounds: optional (doc_start, doc_end), int32 [B, S] each — packed
+    documents: query i sees key j iff doc_start[b, i] <= j <= i."""
+    doc_start, doc_end = _doc_bounds_arg(doc_bounds, causal, alibi_slopes, window,
+                                         rel_bias)
     rel_bias = _rel_bias_arg(rel_bias, alibi_slopes, window)
     window = _window_arg(window, qkv5.shape[1], causal, alibi_slopes)
     return _FlashAttnQKVFn.apply(qkv5, scale, p_drop if training else 0.0, causal,
-                                 kv_len, alibi_slopes, window, rel_bias)
+                                 kv_len, alibi_slopes, window, rel_bias,
+                                 doc_start, doc_end)
 
 
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale, p_drop, causal, kv_len, alibi_slopes=None,
-                window=0, rel_bias=None):
+                window=0, rel_bias=None, doc_start=None, doc_end=None):
         # q, k, v: [B, S, H, D] (may be strided views of the fused qkv buffer)
         seed = draw_seed() if p_drop > 0 else 0
         o, lse = ext().flash_fwd(q, k, v, scale, p_drop, seed, causal, kv_len,
-                                 alibi_slopes, window, rel_bias)
+                                 alibi_slopes, window, rel_bias, doc_start, doc_end)
         if rel_bias is None:
             ctx.save_for_backward(q, k, v, o, lse)
         else:
@@ -174,6 +209,7 @@ class _FlashAttnFn(torch.autograd.Function):
         ctx.kv_len = kv_len
         ctx.alibi_slopes = alibi_slopes
         ctx.window = window
+        ctx.doc_bounds = (doc_start, doc_end)  # int32: no grad flows to them
         ctx.meta = (scale, p_drop, seed, causal)
         return o
 
@@ -184,15 +220,16 @@ class _FlashAttnFn(torch.autograd.Function):
         scale, p_drop, seed, causal = ctx.meta
         grads = ext().flash_bwd(
             q, k, v, o, do.contiguous(), lse, scale, p_drop, seed, causal, None,
-            ctx.kv_len, ctx.alibi_slopes, ctx.window, rel_bias,
+            ctx.kv_len, ctx.alibi_slopes, ctx.window, rel_bias, *ctx.doc_bounds,
         )
         dq, dk, dv = grads[:3]
         d_rel = grads[3] if rel_bias is not None and ctx.needs_input_grad[9] else None
-        return dq, dk, dv, None, None, None, None, None, None, d_rel
+        return dq, dk, dv, None, None, None, None, None, None, d_rel, None, None
 
 
 def flash_attention(q, k, v, scale, p_drop=0.0, causal=True, training=True,
-                    kv_len=None, alibi_slopes=None, window=None, rel_bias=None):
+                    kv_len=None, alibi_slopes=None, window=None, rel_bias=None,
+                    doc_bounds=None):
     """q, k, v: [B, S, H, D] bf16 -> O [B, S, H, D].
 
     alibi_slopes: optional fp32 [H] (query heads) — fused ALiBi bias.
@@ -200,11 +237,18 @@ def flash_attention(q, k, v, scale, p_drop=0.0, causal=True, training=True,
     j <= i with i - j < W (not combinable with alibi_slopes or causal=False).
     rel_bias: optional fp32 [H, Sq+Sk-1] (query heads) — fused Toeplitz bias
     rel_bias[h, kv - q + Sq - 1]; differentiable (its gradient is summed over
-    the batch), not combinable with alibi_slopes or window."""
+    the batch), not combinable with alibi_slopes or window.
+    doc_bounds: optional (doc_start, doc_end), int32 [B, S] each — packed
+    documents: causal attention that stays inside the query's own document
+    (needs Sq == Sk; not combinable with alibi_slopes, window, rel_bias or
+    causal=False)."""
+    doc_start, doc_end = _doc_bounds_arg(doc_bounds, causal, alibi_slopes, window,
+                                         rel_bias)
     rel_bias = _rel_bias_arg(rel_bias, alibi_slopes, window)
     window = _window_arg(window, k.shape[1], causal, alibi_slopes)
     return _FlashAttnFn.apply(q, k, v, scale, p_drop if training else 0.0, causal,
-                              kv_len, alibi_slopes, window, rel_bias)
+                              kv_len, alibi_slopes, window, rel_bias, doc_start,
+                              doc_end)
 
 
 def decode_attention_available(q, head_dim):
