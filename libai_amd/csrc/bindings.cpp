@@ -159,6 +159,20 @@ void quant_fp8_bf16(const void*, void*, const float*, float*, int64_t,
 void res_ln_fwd_bf16(const void*, const void*, const void*, const void*,
                      const void*, void*, void*, int64_t, int, float, bool,
                      hipStream_t);
+bool norm_wave_path(int, int);
+int norm_bwd_fused_blocks(int64_t);
+int ln_bwd_fused_bf16(const void*, const void*, const void*, const float*,
+                       const float*, const void*, void*, float*, bool, int64_t, int,
+                       int, bool, hipStream_t);
+int ln_bwd_fused_f32(const void*, const void*, const void*, const float*,
+                      const float*, const void*, void*, float*, bool, int64_t, int,
+                      int, bool, hipStream_t);
+void res_drop_ln_fwd_bf16(const void*, const void*, const void*, const void*,
+                          const void*, void*, void*, float*, float*, int64_t, int,
+                          float, bool, float, uint64_t, hipStream_t);
+int res_drop_ln_bwd_bf16(const void*, const void*, const void*, const float*,
+                          const float*, const void*, void*, void*, float*, bool, bool,
+                          int64_t, int, int, bool, float, uint64_t, hipStream_t);
 void swiglu_fwd_bf16(const void*, void*, int64_t, int, hipStream_t);
 void swiglu_fwd_f32(const void*, void*, int64_t, int, hipStream_t);
 void swiglu_bwd_bf16(const void*, const void*, void*, int64_t, int, hipStream_t);
@@ -199,14 +213,43 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ln_fwd(
   return {y, mean, rstd};
 }
 
+// `dres` is the gradient arriving on the residual branch of x (the norm op's
+// pass-through output): the result is bf16(bf16(dx_ln) + dres), what a
+// separate add would give.  On the wave path one kernel writes dx and one
+// [P, K*H] partial buffer (kernels/res_norm.hip); `single_pass = false`
+// keeps the dx + wgrad_partial kernel pair there (tests and A/B runs), and
+// wide or ragged rows always take the pair.
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ln_bwd(
     torch::Tensor dy, torch::Tensor x, torch::Tensor gamma, torch::Tensor mean,
-    torch::Tensor rstd, bool rms, bool need_dbeta) {
+    torch::Tensor rstd, bool rms, bool need_dbeta, c10::optional<torch::Tensor> dres,
+    bool single_pass) {
   CHECK_IN(dy);
   CHECK_IN(x);
   const int H = (int)gamma.numel();
   const int64_t R = x.numel() / H;
   auto dx = torch::empty_like(x);
+  if (dres.has_value()) {
+    CHECK_IN(dres.value());
+    TORCH_CHECK(dres->numel() == x.numel() && dres->scalar_type() == x.scalar_type(),
+                "ln_bwd: dres must match x");
+  }
+  if (single_pass && R > 0 && norm_wave_path(H, is_bf16(x) ? 8 : 4)) {
+    const int maxP = norm_bwd_fused_blocks(R);
+    const int64_t K = need_dbeta ? 2 : 1;
+    auto partial =
+        torch::empty({(int64_t)maxP, K * H}, x.options().dtype(torch::kFloat32));
+    auto fn = is_bf16(x) ? ln_bwd_fused_bf16 : ln_bwd_fused_f32;
+    const int P = fn(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(),
+       rms ? nullptr : mean.data_ptr<float>(), rstd.data_ptr<float>(),
+       dres.has_value() ? dres->data_ptr() : nullptr, dx.data_ptr(),
+       partial.data_ptr<float>(), need_dbeta, R, H, maxP, rms, cur_stream());
+    check_launch("ln_bwd_fused");
+    auto folded = partial.narrow(0, 0, P).sum(0);  // one reduction for every gradient
+    auto dg = folded.narrow(0, 0, H).to(gamma.scalar_type());
+    auto dbt = need_dbeta ? folded.narrow(0, H, H).to(gamma.scalar_type())
+                          : torch::Tensor();
+    return {dx, dg, dbt};
+  }
   auto dgamma = torch::empty_like(gamma);
   auto dbeta = need_dbeta ? torch::empty_like(gamma) : torch::Tensor();
   const int64_t gxw = std::max<int64_t>(1, (H / 8 + 255) / 256);
@@ -229,7 +272,99 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ln_bwd(
   // fold was grid-starved at large P)
   dgamma.copy_(partial.narrow(0, 0, P).sum(0));
   if (need_dbeta) dbeta.copy_(partial.narrow(0, P, P).sum(0));
+  if (dres.has_value()) dx.add_(dres->view_as(dx));
   return {dx, dgamma, dbeta};
+}
+
+// ---------------------------------------------------------------------------
+// Training form of bias + dropout + residual + norm (kernels/res_norm.hip):
+// h = (x + bias) * keep + res, y = norm(h); bf16, wave path only.
+// ---------------------------------------------------------------------------
+std::vector<torch::Tensor> res_drop_norm_fwd(
+    torch::Tensor x, c10::optional<torch::Tensor> bias, torch::Tensor res,
+    torch::Tensor gamma, c10::optional<torch::Tensor> beta, double eps, bool rms,
+    double p, int64_t seed) {
+  CHECK_IN(x);
+  CHECK_IN(res);
+  CHECK_IN(gamma);
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "res_drop_norm_fwd: bf16 only");
+  const int H = (int)x.size(-1);
+  TORCH_CHECK(norm_wave_path(H, 8), "res_drop_norm_fwd: width ", H,
+              " is outside the wave path");
+  TORCH_CHECK(res.numel() == x.numel() && res.scalar_type() == x.scalar_type() &&
+                  gamma.numel() == H && gamma.scalar_type() == x.scalar_type(),
+              "res_drop_norm_fwd: res / gamma must match x");
+  const void* bp = nullptr;
+  const void* btp = nullptr;
+  if (bias.has_value()) {
+    CHECK_IN(bias.value());
+    TORCH_CHECK(bias->numel() == H && bias->scalar_type() == x.scalar_type());
+    bp = bias->data_ptr();
+  }
+  if (beta.has_value()) {
+    CHECK_IN(beta.value());
+    TORCH_CHECK(beta->numel() == H && beta->scalar_type() == x.scalar_type());
+    btp = beta->data_ptr();
+  }
+  const int64_t R = x.numel() / H;
+  auto h = torch::empty_like(x);
+  auto y = torch::empty_like(x);
+  auto opts = x.options().dtype(torch::kFloat32);
+  auto mean = rms ? torch::empty({0}, opts) : torch::empty({R}, opts);
+  auto rstd = torch::empty({R}, opts);
+  if (R > 0) {
+    res_drop_ln_fwd_bf16(x.data_ptr(), bp, res.data_ptr(), gamma.data_ptr(), btp,
+                         h.data_ptr(), y.data_ptr(),
+                         rms ? nullptr : mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                         R, H, (float)eps, rms, (float)p, (uint64_t)seed, cur_stream());
+    check_launch("res_drop_norm_fwd");
+  }
+  return {h, y, mean, rstd};
+}
+
+// returns {dh, dx, dgamma, dbeta, dbias}: dh is the residual gradient
+// bf16(bf16(dx_ln) + dres), dx = bf16(dh * keep) the gradient of the GEMM
+// output (the same tensor as dh when p == 0)
+std::vector<torch::Tensor> res_drop_norm_bwd(
+    torch::Tensor dy, torch::Tensor h, torch::Tensor gamma, torch::Tensor mean,
+    torch::Tensor rstd, c10::optional<torch::Tensor> dres, bool rms, bool need_dbeta,
+    bool want_dbias, double p, int64_t seed) {
+  CHECK_IN(dy);
+  CHECK_IN(h);
+  CHECK_IN(gamma);
+  TORCH_CHECK(h.scalar_type() == torch::kBFloat16, "res_drop_norm_bwd: bf16 only");
+  const int H = (int)h.size(-1);
+  TORCH_CHECK(norm_wave_path(H, 8) && gamma.numel() == H,
+              "res_drop_norm_bwd: width ", H, " is outside the wave path");
+  TORCH_CHECK(dy.numel() == h.numel() && dy.scalar_type() == h.scalar_type(),
+              "res_drop_norm_bwd: dy must match h");
+  if (dres.has_value()) {
+    CHECK_IN(dres.value());
+    TORCH_CHECK(dres->numel() == h.numel() && dres->scalar_type() == h.scalar_type(),
+                "res_drop_norm_bwd: dres must match h");
+  }
+  const int64_t R = h.numel() / H;
+  TORCH_CHECK(R > 0, "res_drop_norm_bwd: empty input");
+  TORCH_CHECK(rstd.numel() == R && (rms || mean.numel() == R));
+  auto dh = torch::empty_like(h);
+  auto dx = p > 0 ? torch::empty_like(h) : dh;
+  const int maxP = norm_bwd_fused_blocks(R);
+  const int64_t K = 1 + (need_dbeta ? 1 : 0) + (want_dbias ? 1 : 0);
+  auto partial =
+      torch::empty({(int64_t)maxP, K * H}, h.options().dtype(torch::kFloat32));
+  const int P = res_drop_ln_bwd_bf16(dy.data_ptr(), h.data_ptr(), gamma.data_ptr(),
+                       rms ? nullptr : mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                       dres.has_value() ? dres->data_ptr() : nullptr, dh.data_ptr(),
+                       dx.data_ptr(), partial.data_ptr<float>(), need_dbeta, want_dbias,
+                       R, H, maxP, rms, (float)p, (uint64_t)seed, cur_stream());
+  check_launch("res_drop_norm_bwd");
+  auto folded = partial.narrow(0, 0, P).sum(0);
+  auto dg = folded.narrow(0, 0, H).to(h.scalar_type());
+  auto dbt = need_dbeta ? folded.narrow(0, H, H).to(h.scalar_type()) : torch::Tensor();
+  auto dbs = want_dbias ? folded.narrow(0, (need_dbeta ? 2 : 1) * (int64_t)H, H)
+                              .to(h.scalar_type())
+                        : torch::Tensor();
+  return {dh, dx, dg, dbt, dbs};
 }
 
 // ---------------------------------------------------------------------------
@@ -880,7 +1015,11 @@ void l2norm_sq(torch::Tensor chunks, bool bf16_grads, torch::Tensor out) {
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ln_fwd", &ln_fwd);
-  m.def("ln_bwd", &ln_bwd);
+  m.def("ln_bwd", &ln_bwd, py::arg("dy"), py::arg("x"), py::arg("gamma"),
+        py::arg("mean"), py::arg("rstd"), py::arg("rms"), py::arg("need_dbeta"),
+        py::arg("dres") = py::none(), py::arg("single_pass") = true);
+  m.def("res_drop_norm_fwd", &res_drop_norm_fwd);
+  m.def("res_drop_norm_bwd", &res_drop_norm_bwd);
   m.def("bias_gelu_fwd", &bias_gelu_fwd);
   m.def("bias_gelu_bwd", &bias_gelu_bwd);
   m.def("colsum", &colsum);

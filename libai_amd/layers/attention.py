@@ -132,6 +132,7 @@ class MultiheadAttention(nn.Module):
         position_bias=None,
         static_cache=None,
         position=None,
+        raw_output=False,
     ):
         """attention_mask: [b, sq, sk] bool/uint8, 1 = MASKED (reference semantics).
 
@@ -143,7 +144,11 @@ class MultiheadAttention(nn.Module):
 
         If ``residual`` is given, returns hidden + dropout(out + bias) (the
         fused TransformerLayer path); otherwise applies bias+dropout only.
+        ``raw_output`` (training / no-cache call only) returns the output
+        projection's raw ``(out, bias)`` instead: the layer then runs
+        bias + dropout + residual fused with the norm that follows.
         """
+        assert not raw_output or (past_key_value is None and not use_cache)
         if static_cache is not None:
             # hipGraph-capturable decode: preallocated [b, nh, MAX, hs] caches,
             # device position/length tensors; ONE kv_insert kernel (no-rotate
@@ -218,6 +223,8 @@ class MultiheadAttention(nn.Module):
                 )
                 context = o.reshape(b, s, self.num_heads_local * self.head_size)
                 out, bias = self.dense(context)
+                if raw_output:
+                    return out, bias
                 return bias_dropout_add(
                     out, bias=bias, residual=residual, p=self.output_dropout_prob,
                     training=self.training,
@@ -290,6 +297,8 @@ class MultiheadAttention(nn.Module):
         context = context.permute(0, 2, 1, 3).reshape(b, sq, nh * hs)
 
         out, bias = self.dense(context)
+        if raw_output:
+            return out, bias
         out = bias_dropout_add(
             out, bias=bias, residual=residual, p=self.output_dropout_prob,
             training=self.training,

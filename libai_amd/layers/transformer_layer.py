@@ -42,9 +42,13 @@ class TransformerLayer(nn.Module):
         moe_top_k=2,
         *,
         layer_idx=0,
+        fuse_residual_norm=True,
     ):
         super().__init__()
         self.layer_idx = layer_idx
+        # one switch for the fused residual chain of forward() (plain
+        # attribute: tests and same-process A/Bs flip it on a built layer)
+        self.fuse_residual_norm = fuse_residual_norm
         self.is_decoder = is_decoder
         self.apply_residual_post_layernorm = apply_residual_post_layernorm
         self.sequence_parallel = sequence_parallel
@@ -126,6 +130,23 @@ class TransformerLayer(nn.Module):
                 for p in ln.parameters():
                     p.sequence_parallel_grad = True
 
+    def _fuse_residual_chain(self, past_key_value, use_cache):
+        """The fused chain serves the training / no-cache call of a plain
+        pre-LN block.  Cross-attention decoders, post-LN residuals, KV caches
+        and sequence-parallel shards keep the separate ops; so do, inside the
+        fused ops themselves, CPU, fp32 and rows that are too wide or ragged
+        for the norm kernels' wave path (ops/norm.py)."""
+        return (
+            self.fuse_residual_norm
+            and not self.apply_residual_post_layernorm
+            and not self.is_decoder
+            and not self._sp
+            and not use_cache
+            and past_key_value is None
+            and self.input_layernorm.weight is not None
+            and self.post_attention_layernorm.weight is not None
+        )
+
     def forward(
         self,
         hidden_states,
@@ -167,6 +188,27 @@ class TransformerLayer(nn.Module):
                 self_past, cross_past = past_key_value, None
         else:
             self_past, cross_past = None, None
+
+        if self._fuse_residual_chain(past_key_value, use_cache):
+            # the input norm hands hidden_states on as its second output, so
+            # the residual-branch gradient is added inside its backward
+            # kernel; bias + dropout + residual + post-attention norm run as
+            # one kernel forward and one backward.  Same values and the same
+            # dropout seeds as the separate ops below.
+            from ..ops.norm import bias_dropout_add_norm, layer_norm_residual
+
+            ln_in, ln = self.input_layernorm, self.post_attention_layernorm
+            ln1, residual = layer_norm_residual(hidden_states, ln_in.weight,
+                                                ln_in.bias, ln_in.eps)
+            out, bias = self.self_attention(
+                ln1, attention_mask=attention_mask, position_bias=position_bias,
+                raw_output=True,
+            )
+            h, ln2 = bias_dropout_add_norm(
+                out, bias, residual, ln.weight, ln.bias, ln.eps,
+                p=self.self_attention.output_dropout_prob, training=self.training,
+            )
+            return self.mlp(ln2, residual=h)
 
         ln1 = self.input_layernorm(hidden_states)
         residual = ln1 if self.apply_residual_post_layernorm else hidden_states
