@@ -12,6 +12,9 @@
 #include <tuple>
 #include <vector>
 
+// the extern "C" launchers of csrc/kernels/*.hip
+#include "kernels/launchers.h"
+
 namespace {
 
 hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
@@ -49,142 +52,6 @@ std::tuple<torch::Tensor, torch::Tensor> lt_dgelu_bgrad(torch::Tensor dy,
                                                         torch::Tensor w2,
                                                         torch::Tensor aux);
 bool lt_epilogues_available();
-
-// ---------------------------------------------------------------------------
-// extern "C" launchers from csrc/kernels/*.hip
-// ---------------------------------------------------------------------------
-extern "C" {
-void ln_fwd_bf16(const void*, const void*, const void*, void*, float*, float*, int64_t,
-                 int, float, bool, hipStream_t);
-void ln_fwd_f32(const void*, const void*, const void*, void*, float*, float*, int64_t,
-                int, float, bool, hipStream_t);
-void ln_bwd_dx_bf16(const void*, const void*, const void*, const float*, const float*,
-                    void*, int64_t, int, bool, hipStream_t);
-void ln_bwd_dx_f32(const void*, const void*, const void*, const float*, const float*,
-                   void*, int64_t, int, bool, hipStream_t);
-void ln_bwd_wgrad_bf16(const void*, const void*, const float*, const float*, float*,
-                       float*, void*, void*, int64_t, int, int, bool, hipStream_t);
-void ln_bwd_wgrad_f32(const void*, const void*, const float*, const float*, float*,
-                      float*, void*, void*, int64_t, int, int, bool, hipStream_t);
-void bias_gelu_fwd_bf16(const void*, const void*, void*, int64_t, int, hipStream_t);
-void bias_gelu_fwd_f32(const void*, const void*, void*, int64_t, int, hipStream_t);
-void bias_gelu_bwd_bf16(const void*, const void*, const void*, void*, float*,
-                        int64_t, int, hipStream_t);
-void bias_gelu_bwd_f32(const void*, const void*, const void*, void*, float*,
-                       int64_t, int, hipStream_t);
-int bias_col_grid_rows(int64_t, int, int);
-void bias_dropout_res_fwd_bf16(const void*, const void*, const void*, void*, int64_t,
-                               int, float, uint64_t, hipStream_t);
-void bias_dropout_res_fwd_f32(const void*, const void*, const void*, void*, int64_t,
-                              int, float, uint64_t, hipStream_t);
-void bias_dropout_res_bwd_bf16(const void*, void*, float*, int64_t, int, float,
-                               uint64_t, hipStream_t);
-void bias_dropout_res_bwd_f32(const void*, void*, float*, int64_t, int, float,
-                              uint64_t, hipStream_t);
-void colsum_bf16(const void*, float*, void*, int64_t, int, int, hipStream_t);
-void colsum_f32(const void*, float*, void*, int64_t, int, int, hipStream_t);
-void softmax_fwd_bf16(const void*, const uint8_t*, void*, int64_t, int, int, int, float,
-                      float, uint64_t, bool, hipStream_t);
-void softmax_fwd_f32(const void*, const uint8_t*, void*, int64_t, int, int, int, float,
-                     float, uint64_t, bool, hipStream_t);
-void softmax_bwd_bf16(const void*, const void*, const uint8_t*, void*, int64_t, int,
-                      int, int, float, float, uint64_t, bool, hipStream_t);
-void softmax_bwd_f32(const void*, const void*, const uint8_t*, void*, int64_t, int, int,
-                     int, float, float, uint64_t, bool, hipStream_t);
-void ce_fwd_bf16(const void*, const int64_t*, float*, float*, float*, int64_t, int64_t,
-                 int64_t, int64_t, hipStream_t);
-void ce_fwd_f32(const void*, const int64_t*, float*, float*, float*, int64_t, int64_t,
-                int64_t, int64_t, hipStream_t);
-void ce_bwd_bf16(const void*, const int64_t*, const float*, const float*, const float*,
-                 void*, int64_t, int64_t, int64_t, int64_t, hipStream_t);
-void ce_bwd_f32(const void*, const int64_t*, const float*, const float*, const float*,
-                void*, int64_t, int64_t, int64_t, int64_t, hipStream_t);
-void flash_fwd_bf16(const void*, const void*, const void*, void*, float*,
-                    const int*, int64_t, int64_t, int64_t, int64_t, int64_t,
-                    int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                    int, int, int, int, int, float, float, uint64_t, int, int,
-                    const float*, int, const float*, const int*, hipStream_t);
-void flash_bwd_bf16(const void*, const void*, const void*, const void*, const void*,
-                    const float*, float*, const int*, void*, void*, void*, int64_t,
-                    int64_t,
-                    int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                    int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                    int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                    int64_t, int, int, int, int, int, float, float, uint64_t, int,
-                    int, const float*, int, const float*, float*, const int*,
-                    const int*, hipStream_t);
-void attn_dropout_apply_bf16(void*, int64_t, int64_t, int64_t, float, uint64_t,
-                             hipStream_t);
-void attn_dropout_apply_f32(void*, int64_t, int64_t, int64_t, float, uint64_t,
-                            hipStream_t);
-void embedding_fwd_bf16(const int64_t*, const void*, void*, int64_t, int64_t,
-                        int64_t, int64_t, hipStream_t);
-void embedding_fwd_f32(const int64_t*, const void*, void*, int64_t, int64_t,
-                       int64_t, int64_t, hipStream_t);
-void embedding_bwd_bf16(const int64_t*, const void*, float*, int64_t, int64_t,
-                        int64_t, int64_t, int64_t, hipStream_t);
-void embedding_bwd_f32(const int64_t*, const void*, float*, int64_t, int64_t,
-                       int64_t, int64_t, int64_t, hipStream_t);
-void gemm_dw_bf16(const void*, const void*, float*, void*, int, int64_t, int64_t,
-                  int64_t, int64_t, hipStream_t);
-void flash_decode_bf16(const void*, const void*, const void*, void*, const int*,
-                       int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                       int64_t, int64_t, int64_t, int64_t, int, int, int, int,
-                       float, int, const float*, int, hipStream_t);
-int flash_decode_num_splits(int, int, int);
-void flash_decode_split_bf16(const void*, const void*, const void*, void*,
-                             float*, float*, float*, const int*, int64_t,
-                             int64_t, int64_t, int64_t, int64_t, int64_t,
-                             int64_t, int64_t, int64_t, int64_t, int, int, int,
-                             int, int, float, int, const float*, int,
-                             hipStream_t);
-void rope_fwd_bf16(const void*, void*, const float*, const float*, int64_t, int64_t,
-                   int64_t, int64_t, int64_t, int64_t, int, int, int, int, int,
-                   const int*, int, hipStream_t);
-void rope_fwd_f32(const void*, void*, const float*, const float*, int64_t, int64_t,
-                  int64_t, int64_t, int64_t, int64_t, int, int, int, int, int,
-                  const int*, int, hipStream_t);
-void rope_bwd_bf16(const void*, void*, const float*, const float*, int64_t, int64_t,
-                   int64_t, int64_t, int64_t, int64_t, int, int, int, int, int,
-                   const int*, int, hipStream_t);
-void rope_bwd_f32(const void*, void*, const float*, const float*, int64_t, int64_t,
-                  int64_t, int64_t, int64_t, int64_t, int, int, int, int, int,
-                  const int*, int, hipStream_t);
-void rope_kv_insert_bf16(const void*, const void*, const void*, void*, void*,
-                         void*, const float*, const float*, const long long*,
-                         int, int, int, int, int64_t, int64_t, int64_t, int64_t,
-                         int64_t, int64_t, int64_t, int, int, hipStream_t);
-void quant_fp8_bf16(const void*, void*, const float*, float*, int64_t,
-                    hipStream_t);
-void res_ln_fwd_bf16(const void*, const void*, const void*, const void*,
-                     const void*, void*, void*, int64_t, int, float, bool,
-                     hipStream_t);
-bool norm_wave_path(int, int);
-int norm_bwd_fused_blocks(int64_t);
-int ln_bwd_fused_bf16(const void*, const void*, const void*, const float*,
-                       const float*, const void*, void*, float*, bool, int64_t, int,
-                       int, bool, hipStream_t);
-int ln_bwd_fused_f32(const void*, const void*, const void*, const float*,
-                      const float*, const void*, void*, float*, bool, int64_t, int,
-                      int, bool, hipStream_t);
-void res_drop_ln_fwd_bf16(const void*, const void*, const void*, const void*,
-                          const void*, void*, void*, float*, float*, int64_t, int,
-                          float, bool, float, uint64_t, hipStream_t);
-int res_drop_ln_bwd_bf16(const void*, const void*, const void*, const float*,
-                          const float*, const void*, void*, void*, float*, bool, bool,
-                          int64_t, int, int, bool, float, uint64_t, hipStream_t);
-void swiglu_fwd_bf16(const void*, void*, int64_t, int, hipStream_t);
-void swiglu_fwd_f32(const void*, void*, int64_t, int, hipStream_t);
-void swiglu_bwd_bf16(const void*, const void*, void*, int64_t, int, hipStream_t);
-void swiglu_bwd_f32(const void*, const void*, void*, int64_t, int, hipStream_t);
-int adamw_chunk_elems();
-void adamw_step_bf16(const void*, int, float, float, float, float, float, float, float,
-                     float, hipStream_t);
-void adamw_step_f32(const void*, int, float, float, float, float, float, float, float,
-                    float, hipStream_t);
-void l2norm_sq_bf16(const void*, int, float*, hipStream_t);
-void l2norm_sq_f32(const void*, int, float*, hipStream_t);
-}
 
 // ---------------------------------------------------------------------------
 // LayerNorm / RMSNorm
@@ -564,79 +431,99 @@ torch::Tensor gemm_dw(torch::Tensor dy, torch::Tensor x, int64_t splits) {
 }
 
 
-// optional ALiBi slopes: one fp32 per QUERY head of the call
-static const float* alibi_slopes_ptr(const c10::optional<torch::Tensor>& slopes,
-                                     const torch::Tensor& q, int64_t H) {
-  if (!slopes.has_value()) return nullptr;
-  TORCH_CHECK(slopes->scalar_type() == torch::kFloat32 && slopes->is_cuda() &&
-                  slopes->get_device() == q.get_device() &&
-                  slopes->is_contiguous() && slopes->numel() == H,
-              "alibi_slopes must be a contiguous fp32 tensor of size H (query "
-              "heads) on q's device");
-  return slopes->data_ptr<float>();
+// ---------------------------------------------------------------------------
+// argument checks shared by flash_fwd, flash_bwd and flash_decode
+// ---------------------------------------------------------------------------
+using OptTensor = c10::optional<torch::Tensor>;
+
+// optional per-sequence valid key counts: int32 [B]
+static const int* kv_len_ptr(const OptTensor& kv_len, int64_t B, bool contiguous) {
+  if (!kv_len.has_value()) return nullptr;
+  TORCH_CHECK(kv_len->scalar_type() == torch::kInt32 && kv_len->is_cuda() &&
+                  (!contiguous || kv_len->is_contiguous()) && kv_len->numel() == B,
+              "kv_len must be ", contiguous ? "a contiguous " : "an ",
+              "int32 cuda tensor of size B");
+  return kv_len->data_ptr<int>();
 }
 
-// sliding window (0 = off): query i sees key j iff j <= i and i - j < window.
-// Returns the kernel argument, clamped to the key count (the same mask).
-static int window_arg(int64_t window, bool causal, bool has_alibi, int64_t Sk,
-                      const char* op) {
+// The kernel variant arguments.  At most one of the four is set: the variants
+// do not combine.
+struct VariantPtrs {
+  const float* alibi_slopes = nullptr;  // fp32 [H], one per QUERY head
+  int window = 0;  // query i sees key j iff j <= i and i - j < window; 0 = off
+  const float* rel_bias = nullptr;  // T5 table, fp32 [H, Sq + Sk - 1], one row per
+                                    // QUERY head, entry kv - q + Sq - 1
+  // packed documents, int32 [B, Sq] each: doc_start[b][i] the first token of
+  // the document holding token i, doc_end[b][i] one past its last
+  const int* doc_start = nullptr;
+  const int* doc_end = nullptr;
+};
+
+// Every dtype, shape, device and exclusion check of the variant arguments, in
+// one place and one order.  The window comes back clamped to the key count
+// (the same mask).  flash_decode passes the alibi / window subset.
+static VariantPtrs variant_ptrs(const char* op, const torch::Tensor& q, int64_t B,
+                                int64_t H, int64_t Sq, int64_t Sk, bool causal,
+                                const OptTensor& alibi_slopes, int64_t window,
+                                const OptTensor& rel_bias = c10::nullopt,
+                                const OptTensor& doc_start = c10::nullopt,
+                                const OptTensor& doc_end = c10::nullopt) {
+  VariantPtrs p;
+  auto on_q_device = [&](const torch::Tensor& t, torch::ScalarType dtype) {
+    return t.scalar_type() == dtype && t.is_cuda() &&
+           t.get_device() == q.get_device() && t.is_contiguous();
+  };
+  const bool has_alibi = alibi_slopes.has_value();
+  if (has_alibi) {
+    TORCH_CHECK(on_q_device(*alibi_slopes, torch::kFloat32) &&
+                    alibi_slopes->numel() == H,
+                "alibi_slopes must be a contiguous fp32 tensor of size H (query "
+                "heads) on q's device");
+    p.alibi_slopes = alibi_slopes->data_ptr<float>();
+  }
   TORCH_CHECK(window >= 0, op, ": window must be >= 0 (0 = off)");
-  if (window == 0) return 0;
-  TORCH_CHECK(causal, op, ": a sliding window requires causal attention");
-  TORCH_CHECK(!has_alibi, op,
-              ": a sliding window cannot be combined with alibi_slopes");
-  return (int)std::min<int64_t>(window, std::max<int64_t>(Sk, 1));
-}
-
-// optional relative-position table (T5): fp32 [H, Sq + Sk - 1], one row per
-// QUERY head, entry kv - q + Sq - 1.  Not combinable with ALiBi or a window.
-static const float* rel_bias_ptr(const c10::optional<torch::Tensor>& table,
-                                 const torch::Tensor& q, int64_t H, int64_t Sq,
-                                 int64_t Sk, bool has_alibi, int64_t window,
-                                 const char* op) {
-  if (!table.has_value()) return nullptr;
-  TORCH_CHECK(!has_alibi, op, ": rel_bias cannot be combined with alibi_slopes");
-  TORCH_CHECK(window == 0, op, ": rel_bias cannot be combined with a sliding window");
-  TORCH_CHECK(table->scalar_type() == torch::kFloat32 && table->is_cuda() &&
-                  table->get_device() == q.get_device() && table->is_contiguous() &&
-                  table->dim() == 2 && table->size(0) == H &&
-                  table->size(1) == Sq + Sk - 1,
-              op, ": rel_bias must be a contiguous fp32 tensor of shape "
-              "[H, Sq + Sk - 1] (query heads) on q's device");
-  return table->data_ptr<float>();
-}
-
-// optional packed-document bounds: int32 [B, Sq] each, doc_start[b][i] the
-// first token of the document holding token i, doc_end[b][i] one past its
-// last.  Causal self-attention only; not combinable with ALiBi, a window or
-// a relative-position table.  Sets both pointers, or neither.
-static void doc_bounds_ptrs(const c10::optional<torch::Tensor>& doc_start,
-                            const c10::optional<torch::Tensor>& doc_end,
-                            const torch::Tensor& q, int64_t B, int64_t Sq,
-                            int64_t Sk, bool causal, bool has_alibi,
-                            int64_t window, bool has_rel_bias, const char* op,
-                            const int** ds, const int** de) {
-  *ds = nullptr;
-  *de = nullptr;
+  if (window != 0) {
+    TORCH_CHECK(causal, op, ": a sliding window requires causal attention");
+    TORCH_CHECK(!has_alibi, op,
+                ": a sliding window cannot be combined with alibi_slopes");
+    TORCH_CHECK(Sq == Sk, op, ": a sliding window needs Sq == Sk");
+    p.window = (int)std::min<int64_t>(window, std::max<int64_t>(Sk, 1));
+  }
+  if (rel_bias.has_value()) {
+    TORCH_CHECK(!has_alibi, op, ": rel_bias cannot be combined with alibi_slopes");
+    TORCH_CHECK(window == 0, op,
+                ": rel_bias cannot be combined with a sliding window");
+    TORCH_CHECK(on_q_device(*rel_bias, torch::kFloat32) && rel_bias->dim() == 2 &&
+                    rel_bias->size(0) == H && rel_bias->size(1) == Sq + Sk - 1,
+                op, ": rel_bias must be a contiguous fp32 tensor of shape "
+                "[H, Sq + Sk - 1] (query heads) on q's device");
+    p.rel_bias = rel_bias->data_ptr<float>();
+  }
   TORCH_CHECK(doc_start.has_value() == doc_end.has_value(), op,
               ": doc_start and doc_end must be given together");
-  if (!doc_start.has_value()) return;
-  TORCH_CHECK(causal, op, ": document bounds require causal attention");
-  TORCH_CHECK(Sq == Sk, op, ": document bounds need Sq == Sk");
-  TORCH_CHECK(!has_alibi, op,
-              ": document bounds cannot be combined with alibi_slopes");
-  TORCH_CHECK(window == 0, op,
-              ": document bounds cannot be combined with a sliding window");
-  TORCH_CHECK(!has_rel_bias, op,
-              ": document bounds cannot be combined with rel_bias");
-  for (const torch::Tensor* t : {&doc_start.value(), &doc_end.value()})
-    TORCH_CHECK(t->scalar_type() == torch::kInt32 && t->is_cuda() &&
-                    t->get_device() == q.get_device() && t->is_contiguous() &&
-                    t->dim() == 2 && t->size(0) == B && t->size(1) == Sq,
-                op, ": doc_start / doc_end must be contiguous int32 tensors of "
-                "shape [B, Sq] on q's device");
-  *ds = doc_start->data_ptr<int>();
-  *de = doc_end->data_ptr<int>();
+  if (doc_start.has_value()) {
+    TORCH_CHECK(causal, op, ": document bounds require causal attention");
+    TORCH_CHECK(Sq == Sk, op, ": document bounds need Sq == Sk");
+    TORCH_CHECK(!has_alibi, op,
+                ": document bounds cannot be combined with alibi_slopes");
+    TORCH_CHECK(window == 0, op,
+                ": document bounds cannot be combined with a sliding window");
+    TORCH_CHECK(!rel_bias.has_value(), op,
+                ": document bounds cannot be combined with rel_bias");
+    for (const torch::Tensor* t : {&doc_start.value(), &doc_end.value()})
+      TORCH_CHECK(on_q_device(*t, torch::kInt32) && t->dim() == 2 &&
+                      t->size(0) == B && t->size(1) == Sq,
+                  op, ": doc_start / doc_end must be contiguous int32 tensors of "
+                  "shape [B, Sq] on q's device");
+    p.doc_start = doc_start->data_ptr<int>();
+    p.doc_end = doc_end->data_ptr<int>();
+  }
+  return p;
+}
+
+// pointer and (batch, seq, head) element strides of a [B, S, H, D] tensor
+static StridedBSHD strided(const torch::Tensor& t) {
+  return {t.data_ptr(), t.stride(0), t.stride(1), t.stride(2)};
 }
 
 // ---------------------------------------------------------------------------
@@ -654,15 +541,13 @@ torch::Tensor flash_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   const int Skv = (int)k.size(2), Hkv = (int)k.size(1);
   TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
   TORCH_CHECK(H % Hkv == 0 && (int)v.size(1) == Hkv);
-  const int* kvl = nullptr;
-  if (kv_len.has_value()) {
-    TORCH_CHECK(kv_len->scalar_type() == torch::kInt32 && kv_len->is_cuda() &&
-                kv_len->numel() == B);
-    kvl = kv_len->data_ptr<int>();
-  }
-  const float* slopes = alibi_slopes_ptr(alibi_slopes, q, H);
-  // decode is causal by construction: the query is the last cached key
-  const int win = window_arg(window, true, slopes != nullptr, Skv, "flash_decode");
+  const int* kvl = kv_len_ptr(kv_len, B, /*contiguous=*/false);
+  // decode is causal by construction: the query is the last cached key, so it
+  // stands at row Skv - 1 of a square problem
+  const VariantPtrs var =
+      variant_ptrs("flash_decode", q, B, H, Skv, Skv, true, alibi_slopes, window);
+  const float* slopes = var.alibi_slopes;
+  const int win = var.window;
   auto o = torch::empty({B, H, 1, D}, q.options());
   const int S = flash_decode_num_splits(B, H, Skv);
   if (S > 1) {
@@ -739,6 +624,37 @@ torch::Tensor embedding_bwd(torch::Tensor ids, torch::Tensor dout,
 // ---------------------------------------------------------------------------
 // flash attention
 // ---------------------------------------------------------------------------
+// the launch arguments the forward and the backward share, each stride next
+// to the tensor it came from
+static FlashFwdArgs flash_args(const torch::Tensor& q, const torch::Tensor& k,
+                               const torch::Tensor& v, const torch::Tensor& o,
+                               const torch::Tensor& lse, const int* kv_len,
+                               double scale, double p_drop, int64_t seed, bool causal,
+                               const VariantPtrs& var) {
+  FlashFwdArgs a{};
+  a.q = strided(q);
+  a.k = strided(k);
+  a.v = strided(v);
+  a.o = strided(o);
+  a.lse = lse.data_ptr<float>();
+  a.kv_len = kv_len;
+  a.B = (int)q.size(0);
+  a.H = (int)q.size(2);
+  a.Sq = (int)q.size(1);
+  a.Sk = (int)k.size(1);
+  a.D = (int)q.size(3);
+  a.kv_group = (int)(q.size(2) / k.size(2));
+  a.scale = (float)scale;
+  a.p_drop = (float)p_drop;
+  a.seed = (uint64_t)seed;
+  a.causal = causal ? 1 : 0;
+  a.alibi_slopes = var.alibi_slopes;
+  a.window = var.window;
+  a.rel_bias = var.rel_bias;
+  a.doc_start = var.doc_start;
+  return a;
+}
+
 std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tensor k,
                                                    torch::Tensor v, double scale,
                                                    double p_drop, int64_t seed,
@@ -749,13 +665,7 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
                                                    c10::optional<torch::Tensor> rel_bias,
                                                    c10::optional<torch::Tensor> doc_start,
                                                    c10::optional<torch::Tensor> doc_end) {
-  const int* kvl = nullptr;
-  if (kv_len.has_value()) {
-    TORCH_CHECK(kv_len->scalar_type() == torch::kInt32 && kv_len->is_cuda() &&
-                    kv_len->is_contiguous() && kv_len->numel() == q.size(0),
-                "kv_len must be a contiguous int32 cuda tensor of size B");
-    kvl = kv_len->data_ptr<int>();
-  }
+  const int* kvl = kv_len_ptr(kv_len, q.size(0), /*contiguous=*/true);
   // q/k/v: [B, S, H, D] (strided views into a fused qkv buffer are fine; the
   // last dim must be contiguous and 16B-aligned)
   TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4);
@@ -768,23 +678,14 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
   TORCH_CHECK(Sk % 8 == 0, "Sk must be a multiple of 8");
   TORCH_CHECK(Hkv > 0 && H % Hkv == 0 && (int)v.size(2) == Hkv,
               "GQA head counts: H divisible by Hkv, v matches k");
-  const int kv_group = H / Hkv;
-  const float* slopes = alibi_slopes_ptr(alibi_slopes, q, H);
-  const int win = window_arg(window, causal, slopes != nullptr, Sk, "flash_fwd");
-  TORCH_CHECK(win == 0 || Sq == Sk, "flash_fwd: a sliding window needs Sq == Sk");
-  const float* relb =
-      rel_bias_ptr(rel_bias, q, H, Sq, Sk, slopes != nullptr, window, "flash_fwd");
-  const int *docs = nullptr, *doce = nullptr;
-  doc_bounds_ptrs(doc_start, doc_end, q, B, Sq, Sk, causal, slopes != nullptr,
-                  window, relb != nullptr, "flash_fwd", &docs, &doce);
+  const VariantPtrs var = variant_ptrs("flash_fwd", q, B, H, Sq, Sk, causal,
+                                       alibi_slopes, window, rel_bias, doc_start,
+                                       doc_end);
   auto o = torch::empty({B, Sq, H, D}, q.options());
   auto lse = torch::empty({B, H, Sq}, q.options().dtype(torch::kFloat32));
-  flash_fwd_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                 lse.data_ptr<float>(), kvl, q.stride(0), q.stride(1), q.stride(2),
-                 k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1),
-                 v.stride(2), o.stride(0), o.stride(1), o.stride(2), B, H, Sq, Sk, D,
-                 (float)scale, (float)p_drop, (uint64_t)seed, causal ? 1 : 0,
-                 kv_group, slopes, win, relb, docs, cur_stream());
+  const FlashFwdArgs a =
+      flash_args(q, k, v, o, lse, kvl, scale, p_drop, seed, causal, var);
+  flash_fwd_bf16(a, cur_stream());
   check_launch("flash_fwd");
   return {o, lse};
 }
@@ -799,33 +700,21 @@ py::tuple flash_bwd(
     c10::optional<torch::Tensor> alibi_slopes, int64_t window,
     c10::optional<torch::Tensor> rel_bias, c10::optional<torch::Tensor> doc_start,
     c10::optional<torch::Tensor> doc_end) {
-  const int* kvl = nullptr;
-  if (kv_len.has_value()) {
-    TORCH_CHECK(kv_len->scalar_type() == torch::kInt32 && kv_len->is_cuda() &&
-                    kv_len->is_contiguous() && kv_len->numel() == q.size(0),
-                "kv_len must be a contiguous int32 cuda tensor of size B");
-    kvl = kv_len->data_ptr<int>();
-  }
+  const int* kvl = kv_len_ptr(kv_len, q.size(0), /*contiguous=*/true);
   const int B = (int)q.size(0), Sq = (int)q.size(1), H = (int)q.size(2),
             D = (int)q.size(3);
   const int Sk = (int)k.size(1), Hkv = (int)k.size(2);
-  const int kv_group = H / Hkv;
-  const float* slopes = alibi_slopes_ptr(alibi_slopes, q, H);
-  const int win = window_arg(window, causal, slopes != nullptr, Sk, "flash_bwd");
-  TORCH_CHECK(win == 0 || Sq == Sk, "flash_bwd: a sliding window needs Sq == Sk");
-  const float* relb =
-      rel_bias_ptr(rel_bias, q, H, Sq, Sk, slopes != nullptr, window, "flash_bwd");
-  const int *docs = nullptr, *doce = nullptr;
-  doc_bounds_ptrs(doc_start, doc_end, q, B, Sq, Sk, causal, slopes != nullptr,
-                  window, relb != nullptr, "flash_bwd", &docs, &doce);
+  const VariantPtrs var = variant_ptrs("flash_bwd", q, B, H, Sq, Sk, causal,
+                                       alibi_slopes, window, rel_bias, doc_start,
+                                       doc_end);
   // the dQ kernel accumulates into it with atomics: zero-filled here
   torch::Tensor d_relb;
-  if (relb != nullptr) d_relb = torch::zeros_like(rel_bias.value());
+  if (var.rel_bias != nullptr) d_relb = torch::zeros_like(rel_bias.value());
   TORCH_CHECK(dout.is_contiguous() && o.is_contiguous());
   torch::Tensor dq, dk, dv;
   if (dqkv.has_value()) {
     // [B, S, H, 3, D] fused grad buffer: write q/k/v grads in place
-    TORCH_CHECK(kv_group == 1, "packed dqkv implies MHA");
+    TORCH_CHECK(H / Hkv == 1, "packed dqkv implies MHA");
     auto g = dqkv.value();
     dq = g.select(3, 0);
     dk = g.select(3, 1);
@@ -836,19 +725,19 @@ py::tuple flash_bwd(
     dv = torch::empty({B, Sk, Hkv, D}, q.options());
   }
   auto drow = torch::empty({B, H, Sq}, q.options().dtype(torch::kFloat32));
-  flash_bwd_bf16(
-      q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
-      lse.data_ptr<float>(), drow.data_ptr<float>(), kvl, dq.data_ptr(),
-      dk.data_ptr(), dv.data_ptr(), q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
-      k.stride(2), v.stride(0), v.stride(1), v.stride(2), o.stride(0), o.stride(1),
-      o.stride(2), dout.stride(0), dout.stride(1), dout.stride(2), dq.stride(0),
-      dq.stride(1), dq.stride(2), dk.stride(0), dk.stride(1), dk.stride(2),
-      dv.stride(0), dv.stride(1), dv.stride(2), B, H, Sq, Sk, D, (float)scale,
-      (float)p_drop, (uint64_t)seed, causal ? 1 : 0, kv_group, slopes, win, relb,
-      relb != nullptr ? d_relb.data_ptr<float>() : nullptr, docs, doce,
-      cur_stream());
+  FlashBwdArgs a{};
+  static_cast<FlashFwdArgs&>(a) =
+      flash_args(q, k, v, o, lse, kvl, scale, p_drop, seed, causal, var);
+  a.dout = strided(dout);
+  a.dq = strided(dq);
+  a.dk = strided(dk);
+  a.dv = strided(dv);
+  a.drow_ws = drow.data_ptr<float>();
+  a.d_rel_bias = var.rel_bias != nullptr ? d_relb.data_ptr<float>() : nullptr;
+  a.doc_end = var.doc_end;
+  flash_bwd_bf16(a, cur_stream());
   check_launch("flash_bwd");
-  if (relb != nullptr) return py::make_tuple(dq, dk, dv, d_relb);
+  if (var.rel_bias != nullptr) return py::make_tuple(dq, dk, dv, d_relb);
   return py::make_tuple(dq, dk, dv);
 }
 

@@ -43,6 +43,8 @@ def build(force=False, verbose=True):
 
     os.makedirs(BUILD, exist_ok=True)
     common_h = os.path.join(KERNELS, "common.h")
+    # the launcher ABI: included by every kernel file and by bindings.cpp
+    launchers_h = os.path.join(KERNELS, "launchers.h")
     objs = []
 
     for fname in sorted(os.listdir(KERNELS)):
@@ -51,7 +53,7 @@ def build(force=False, verbose=True):
         src = os.path.join(KERNELS, fname)
         obj = os.path.join(BUILD, fname[:-4] + ".o")
         objs.append(obj)
-        if not force and _newer(obj, src, common_h):
+        if not force and _newer(obj, src, common_h, launchers_h):
             continue
         _run(
             [
@@ -75,7 +77,8 @@ def build(force=False, verbose=True):
     for cpp_name in ("bindings.cpp", "gemm_lt.cpp"):
         cpp_src = os.path.join(CSRC, cpp_name)
         cpp_obj = os.path.join(BUILD, cpp_name[:-4] + ".o")
-        if force or not _newer(cpp_obj, cpp_src):
+        deps = (cpp_src, launchers_h) if cpp_name == "bindings.cpp" else (cpp_src,)
+        if force or not _newer(cpp_obj, *deps):
             cmd = [
                 "g++",
                 "-O2",

@@ -11,6 +11,7 @@
 // multi-tensor squared-L2 kernel + a host-side scalar, applied in the update
 // via grad_scale (one pass over grads total).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

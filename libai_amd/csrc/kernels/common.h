@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #define WAVE 64  // CDNA wavefront width (hard-coded per gfx950 guide)
 
 // ---------------------------------------------------------------------------
@@ -215,3 +217,43 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 }
 
 #define CDIV(a, b) (((a) + (b)-1) / (b))
+
+// ---------------------------------------------------------------------------
+// Flash-attention kernel variants (flash_attn.hip, flash_decode.hip).  The
+// binding rejects every combination, so the choice is one value, not a cross
+// product: the kernels are templated on <int D, FlashVariant V> and derive
+// their ALIBI / WINDOW / RELB / DOCS switches from V.
+// ---------------------------------------------------------------------------
+enum class FlashVariant : int { kPlain, kAlibi, kWindow, kRelBias, kDocs };
+
+// the variant of a launch, from its (already clamped) variant arguments
+inline FlashVariant flash_variant(const float* alibi_slopes, int window,
+                                  const float* rel_bias, const int* doc_start) {
+  if (alibi_slopes != nullptr) return FlashVariant::kAlibi;
+  if (window > 0) return FlashVariant::kWindow;
+  if (rel_bias != nullptr) return FlashVariant::kRelBias;
+  if (doc_start != nullptr) return FlashVariant::kDocs;
+  return FlashVariant::kPlain;
+}
+
+// calls f(integral_constant<int, D>, integral_constant<FlashVariant, v>) for
+// the head sizes the kernels are built for; any other D launches nothing
+template <class F>
+void flash_dispatch(int D, FlashVariant v, F&& f) {
+  auto on_d = [&](auto d) {
+#define FLASH_VARIANT_CASE(NAME)                                             \
+  case FlashVariant::NAME:                                                   \
+    f(d, std::integral_constant<FlashVariant, FlashVariant::NAME>{});        \
+    break;
+    switch (v) {
+      FLASH_VARIANT_CASE(kPlain)
+      FLASH_VARIANT_CASE(kAlibi)
+      FLASH_VARIANT_CASE(kWindow)
+      FLASH_VARIANT_CASE(kRelBias)
+      FLASH_VARIANT_CASE(kDocs)
+    }
+#undef FLASH_VARIANT_CASE
+  };
+  if (D == 64) on_d(std::integral_constant<int, 64>{});
+  else if (D == 128) on_d(std::integral_constant<int, 128>{});
+}

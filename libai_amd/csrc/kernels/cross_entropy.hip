@@ -10,6 +10,7 @@
 //   sumexp_global = allreduce_sum(sumexp_local * exp(max_local - max_global))
 // Backward is one read+write pass: d logits = g * (softmax - onehot).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -15,6 +15,7 @@
 // accumulation is HIGHER precision than bf16 in-place adds), followed by a
 // torch-side cast into the bf16 grad view.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

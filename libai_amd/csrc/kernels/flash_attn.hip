@@ -44,6 +44,7 @@
 // the class branch: only the element values merge after it (accumulators
 // merged through the branch cost 400-600 B/lane of scratch).
 #include "common.h"
+#include "launchers.h"
 
 #include <type_traits>
 
@@ -235,6 +236,8 @@ __device__ __forceinline__ int block_tile() {
 // ===========================================================================
 // forward
 // ===========================================================================
+// The kernels are templated on one FlashVariant V (common.h; the variants do
+// not combine) and derive the four switches below from it.
 // ALIBI: compile-time variant that adds slope[h] * (kv - q) to every
 // pre-softmax score (fp32, one slope per QUERY head).  The (kv - q) form is
 // row-shift-equivalent to BLOOM's slope * kv under softmax, is bounded by the
@@ -307,7 +310,7 @@ __device__ __forceinline__ void relb_flush(float* ring, float* __restrict__ grow
   }
 }
 
-template <int D, bool ALIBI, bool WINDOW, bool RELB, bool DOCS>
+template <int D, FlashVariant V>
 __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, bf16_t* __restrict__ o, float* __restrict__ lse,
@@ -317,6 +320,9 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     float scale, float p_drop, uint64_t seed, int causal, int kv_group,
     const float* __restrict__ alibi_slopes, int window,
     const float* __restrict__ rel_bias, const int* __restrict__ doc_start) {
+  constexpr bool ALIBI = V == FlashVariant::kAlibi,
+                 WINDOW = V == FlashVariant::kWindow,
+                 RELB = V == FlashVariant::kRelBias, DOCS = V == FlashVariant::kDocs;
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
 
@@ -626,7 +632,7 @@ __global__ void rowdot_kernel(const bf16_t* __restrict__ dout,
 // restarts per GQA query head; all its conditions are workgroup-uniform.  The
 // staged values, the compute body and their order are those of the plain
 // loop, so dK and dV do not change by a bit.
-template <int D, bool ALIBI, bool WINDOW, bool RELB, bool DOCS>
+template <int D, FlashVariant V>
 __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
@@ -640,6 +646,9 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
     int causal, int kv_group, const float* __restrict__ alibi_slopes,
     int window, const float* __restrict__ rel_bias,
     const int* __restrict__ doc_end) {
+  constexpr bool ALIBI = V == FlashVariant::kAlibi,
+                 WINDOW = V == FlashVariant::kWindow,
+                 RELB = V == FlashVariant::kRelBias, DOCS = V == FlashVariant::kDocs;
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
   // D=64: 64-row staging tiles.  D=128: 32-row tiles.
@@ -1059,7 +1068,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kv_kernel(
 // of the next staging round, between the two barriers the loop already has,
 // and the rest behind the loop: one global fp32 atomic per (workgroup,
 // touched diagonal), whatever the sequence length.
-template <int D, bool ALIBI, bool WINDOW, bool RELB, bool DOCS>
+template <int D, FlashVariant V>
 __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
@@ -1072,6 +1081,9 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
     int causal, int kv_group, const float* __restrict__ alibi_slopes,
     int window, const float* __restrict__ rel_bias,
     float* __restrict__ d_rel_bias, const int* __restrict__ doc_start) {
+  constexpr bool ALIBI = V == FlashVariant::kAlibi,
+                 WINDOW = V == FlashVariant::kWindow,
+                 RELB = V == FlashVariant::kRelBias, DOCS = V == FlashVariant::kDocs;
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
   constexpr int KVTILE = (D == 64) ? 2 * QB : QB;
@@ -1349,133 +1361,73 @@ __global__ void attn_dropout_apply_kernel(typename E::T* __restrict__ x, int64_t
 
 }  // namespace
 
-extern "C" void flash_fwd_bf16(const void* q, const void* k, const void* v, void* o,
-                               float* lse, const int* kv_len, int64_t q_sb,
-                               int64_t q_ss, int64_t q_sh, int64_t k_sb,
-                               int64_t k_ss, int64_t k_sh, int64_t v_sb,
-                               int64_t v_ss, int64_t v_sh, int64_t o_sb, int64_t o_ss,
-                               int64_t o_sh, int B, int H, int Sq, int Sk, int D,
-                               float scale, float p_drop, uint64_t seed, int causal,
-                               int kv_group, const float* alibi_slopes,
-                               int window, const float* rel_bias,
-                               const int* doc_start, hipStream_t stream) {
-  dim3 grid(CDIV(Sq, QBLK), B * H);
-  dim3 block(256);
-#define FWD_ARGS                                                                     \
-  (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, kv_len,     \
-      q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, o_sb, o_ss, o_sh, H, Sq, \
-      Sk, scale, p_drop, seed, causal, kv_group, alibi_slopes, window, rel_bias,     \
-      doc_start
-  // the binding rejects window, ALiBi, a relative-position table and packed
-  // documents in any combination: no cross product
-  const bool docs = doc_start != nullptr;
-  const bool alibi = alibi_slopes != nullptr;
-  const bool relb = rel_bias != nullptr;
-  window = window > 0 ? min(window, max(Sq, Sk)) : 0;  // same mask, no overflow
-  if (D == 64) {
-    if (alibi)
-      flash_fwd_kernel<64, true, false, false, false>
-          <<<grid, block, 0, stream>>>(FWD_ARGS);
-    else if (window > 0)
-      flash_fwd_kernel<64, false, true, false, false>
-          <<<grid, block, 0, stream>>>(FWD_ARGS);
-    else if (relb)
-      flash_fwd_kernel<64, false, false, true, false>
-          <<<grid, block, 0, stream>>>(FWD_ARGS);
-    else if (docs)
-      flash_fwd_kernel<64, false, false, false, true>
-          <<<grid, block, 0, stream>>>(FWD_ARGS);
-    else
-      flash_fwd_kernel<64, false, false, false, false>
-          <<<grid, block, 0, stream>>>(FWD_ARGS);
-  } else if (D == 128) {
-    if (alibi)
-      flash_fwd_kernel<128, true, false, false, false>
-          <<<grid, block, 0, stream>>>(FWD_ARGS);
-    else if (window > 0)
-      flash_fwd_kernel<128, false, true, false, false>
-          <<<grid, block, 0, stream>>>(FWD_ARGS);
-    else if (relb)
-      flash_fwd_kernel<128, false, false, true, false>
-          <<<grid, block, 0, stream>>>(FWD_ARGS);
-    else if (docs)
-      flash_fwd_kernel<128, false, false, false, true>
-          <<<grid, block, 0, stream>>>(FWD_ARGS);
-    else
-      flash_fwd_kernel<128, false, false, false, false>
-          <<<grid, block, 0, stream>>>(FWD_ARGS);
-  }
-#undef FWD_ARGS
+// the kernels take typed pointers; the ABI struct carries void*
+static const bf16_t* in(const StridedBSHD& t) { return (const bf16_t*)t.ptr; }
+static bf16_t* out(const StridedBSHD& t) { return (bf16_t*)t.ptr; }
+
+// same mask, no overflow in the kernels' row arithmetic
+static int clamp_window(int window, int Sq, int Sk) {
+  return window > 0 ? min(window, max(Sq, Sk)) : 0;
 }
 
-extern "C" void flash_bwd_bf16(
-    const void* q, const void* k, const void* v, const void* o, const void* dout,
-    const float* lse, float* drow_ws, const int* kv_len, void* dq, void* dk,
-    void* dv, int64_t q_sb,
-    int64_t q_ss, int64_t q_sh, int64_t k_sb, int64_t k_ss, int64_t k_sh,
-    int64_t v_sb, int64_t v_ss, int64_t v_sh, int64_t o_sb, int64_t o_ss,
-    int64_t o_sh, int64_t do_sb, int64_t do_ss, int64_t do_sh, int64_t dq_sb,
-    int64_t dq_ss, int64_t dq_sh, int64_t dk_sb, int64_t dk_ss, int64_t dk_sh,
-    int64_t dv_sb, int64_t dv_ss, int64_t dv_sh, int B, int H, int Sq, int Sk, int D,
-    float scale, float p_drop, uint64_t seed, int causal, int kv_group,
-    const float* alibi_slopes, int window, const float* rel_bias,
-    float* d_rel_bias, const int* doc_start, const int* doc_end,
-    hipStream_t stream) {
+extern "C" void flash_fwd_bf16(const FlashFwdArgs& a, hipStream_t stream) {
+  const dim3 grid(CDIV(a.Sq, QBLK), a.B * a.H), block(256);
+  const int window = clamp_window(a.window, a.Sq, a.Sk);
+  const FlashVariant variant =
+      flash_variant(a.alibi_slopes, window, a.rel_bias, a.doc_start);
+  flash_dispatch(a.D, variant, [&](auto dc, auto vc) {
+    flash_fwd_kernel<decltype(dc)::value, decltype(vc)::value>
+        <<<grid, block, 0, stream>>>(
+            in(a.q), in(a.k), in(a.v), out(a.o), a.lse, a.kv_len,
+            a.q.sb, a.q.ss, a.q.sh,
+            a.k.sb, a.k.ss, a.k.sh,
+            a.v.sb, a.v.ss, a.v.sh,
+            a.o.sb, a.o.ss, a.o.sh,
+            a.H, a.Sq, a.Sk, a.scale, a.p_drop, a.seed, a.causal, a.kv_group,
+            a.alibi_slopes, window, a.rel_bias, a.doc_start);
+  });
+}
+
+extern "C" void flash_bwd_bf16(const FlashBwdArgs& a, hipStream_t stream) {
+  const dim3 block(256);
+  const int Hkv = a.H / a.kv_group;  // bwd_kv grid spans the KV heads
+  const dim3 grid_kv(CDIV(a.Sk, QBLK), a.B * Hkv), grid_q(CDIV(a.Sq, QBLK), a.B * a.H);
+  const int window = clamp_window(a.window, a.Sq, a.Sk);
+  const FlashVariant variant =
+      flash_variant(a.alibi_slopes, window, a.rel_bias, a.doc_start);
   // Drow = rowsum(dO * O)  (dO and O share layout; use dO's strides for both:
   // the wrapper guarantees o was allocated with the same layout)
-  {
-    int rpw = 64 / (D / 8);
-    int64_t rows = (int64_t)B * Sq * H;
-    int64_t waves = CDIV(rows, rpw);
-    uint32_t blocks = (uint32_t)CDIV(waves * 64, 256);
-    if (D == 64)
-      rowdot_kernel<64><<<dim3(blocks), 256, 0, stream>>>(
-          (const bf16_t*)dout, (const bf16_t*)o, drow_ws, do_sb, do_ss, do_sh, H, Sq,
-          rows);
-    else
-      rowdot_kernel<128><<<dim3(blocks), 256, 0, stream>>>(
-          (const bf16_t*)dout, (const bf16_t*)o, drow_ws, do_sb, do_ss, do_sh, H, Sq,
-          rows);
-  }
-#define BWD_ARGS_KV                                                                  \
-  (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse,    \
-      drow_ws, kv_len, (bf16_t*)dk, (bf16_t*)dv, q_sb, q_ss, q_sh, k_sb, k_ss,       \
-      k_sh, v_sb, v_ss, v_sh, do_sb, do_ss, do_sh, dk_sb, dk_ss, dk_sh, dv_sb,       \
-      dv_ss, dv_sh, H, Sq, Sk, scale, p_drop, seed, causal, kv_group,                \
-      alibi_slopes, window, rel_bias, doc_end
-#define BWD_ARGS_Q                                                                   \
-  (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse,    \
-      drow_ws, kv_len, (bf16_t*)dq, q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss,  \
-      v_sh, do_sb, do_ss, do_sh, dq_sb, dq_ss, dq_sh, H, Sq, Sk, scale, p_drop,      \
-      seed, causal, kv_group, alibi_slopes, window, rel_bias, d_rel_bias, doc_start
-  dim3 block(256);
-  const int Hkv = H / kv_group;  // bwd_kv grid spans the KV heads
-  const dim3 grid_kv(CDIV(Sk, QBLK), B * Hkv), grid_q(CDIV(Sq, QBLK), B * H);
-#define BWD_LAUNCH(DD, AL, WIN, RB, DOC)                                             \
-  do {                                                                               \
-    flash_bwd_kv_kernel<DD, AL, WIN, RB, DOC>                                        \
-        <<<grid_kv, block, 0, stream>>>(BWD_ARGS_KV);                                \
-    flash_bwd_q_kernel<DD, AL, WIN, RB, DOC>                                         \
-        <<<grid_q, block, 0, stream>>>(BWD_ARGS_Q);                                  \
-  } while (0)
-  const bool alibi = alibi_slopes != nullptr;
-  const bool relb = rel_bias != nullptr;
-  const bool docs = doc_start != nullptr;
-  window = window > 0 ? min(window, max(Sq, Sk)) : 0;  // same mask, no overflow
-  if (D == 64) {
-    if (alibi) BWD_LAUNCH(64, true, false, false, false);
-    else if (window > 0) BWD_LAUNCH(64, false, true, false, false);
-    else if (relb) BWD_LAUNCH(64, false, false, true, false);
-    else if (docs) BWD_LAUNCH(64, false, false, false, true);
-    else BWD_LAUNCH(64, false, false, false, false);
-  } else if (D == 128) {
-    if (alibi) BWD_LAUNCH(128, true, false, false, false);
-    else if (window > 0) BWD_LAUNCH(128, false, true, false, false);
-    else if (relb) BWD_LAUNCH(128, false, false, true, false);
-    else if (docs) BWD_LAUNCH(128, false, false, false, true);
-    else BWD_LAUNCH(128, false, false, false, false);
-  }
-#undef BWD_LAUNCH
+  const int rpw = 64 / (a.D / 8);
+  const int64_t rows = (int64_t)a.B * a.Sq * a.H;
+  const uint32_t rowdot_blocks = (uint32_t)CDIV(CDIV(rows, rpw) * 64, 256);
+  flash_dispatch(a.D, variant, [&](auto dc, auto vc) {
+    constexpr int DD = decltype(dc)::value;
+    constexpr FlashVariant VV = decltype(vc)::value;
+    rowdot_kernel<DD><<<dim3(rowdot_blocks), 256, 0, stream>>>(
+        in(a.dout), in(a.o), a.drow_ws, a.dout.sb, a.dout.ss, a.dout.sh, a.H, a.Sq,
+        rows);
+    flash_bwd_kv_kernel<DD, VV><<<grid_kv, block, 0, stream>>>(
+        in(a.q), in(a.k), in(a.v), in(a.dout), a.lse, a.drow_ws, a.kv_len,
+        out(a.dk), out(a.dv),
+        a.q.sb, a.q.ss, a.q.sh,
+        a.k.sb, a.k.ss, a.k.sh,
+        a.v.sb, a.v.ss, a.v.sh,
+        a.dout.sb, a.dout.ss, a.dout.sh,
+        a.dk.sb, a.dk.ss, a.dk.sh,
+        a.dv.sb, a.dv.ss, a.dv.sh,
+        a.H, a.Sq, a.Sk, a.scale, a.p_drop, a.seed, a.causal, a.kv_group,
+        a.alibi_slopes, window, a.rel_bias, a.doc_end);
+    flash_bwd_q_kernel<DD, VV><<<grid_q, block, 0, stream>>>(
+        in(a.q), in(a.k), in(a.v), in(a.dout), a.lse, a.drow_ws, a.kv_len,
+        out(a.dq),
+        a.q.sb, a.q.ss, a.q.sh,
+        a.k.sb, a.k.ss, a.k.sh,
+        a.v.sb, a.v.ss, a.v.sh,
+        a.dout.sb, a.dout.ss, a.dout.sh,
+        a.dq.sb, a.dq.ss, a.dq.sh,
+        a.H, a.Sq, a.Sk, a.scale, a.p_drop, a.seed, a.causal, a.kv_group,
+        a.alibi_slopes, window, a.rel_bias, a.d_rel_bias, a.doc_start);
+  });
 }
 
 #define ATTN_DROP_LAUNCHER(SUFF, ETYPE)                                            \

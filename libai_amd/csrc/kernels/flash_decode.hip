@@ -13,6 +13,7 @@
 // coalesced 128B line of V — and the 4 wave states merge through LDS.
 // GQA: query head h reads kv head h / kv_group.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -26,7 +27,7 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 // the keys [max(0, skv - window), skv).  64-key chunks that end below the
 // window start are skipped whole (wave-uniform); keys below it inside a
 // straddling chunk get the sentinel (p = 0; the V loop is left as it is).
-template <int D, bool ALIBI, bool WINDOW>
+template <int D, FlashVariant V>
 __global__ __launch_bounds__(256, 4) void flash_decode_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, bf16_t* __restrict__ o,
@@ -34,6 +35,8 @@ __global__ __launch_bounds__(256, 4) void flash_decode_kernel(
     int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss, int64_t v_sh,
     int64_t o_sb, int64_t o_sh, int H, int Skv, float scale, int kv_group,
     const float* __restrict__ alibi_slopes, int window) {
+  constexpr bool ALIBI = V == FlashVariant::kAlibi,
+                 WINDOW = V == FlashVariant::kWindow;
   constexpr int DPL = D / 64;  // dims per lane
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -158,7 +161,7 @@ constexpr int SPLIT_KEYS = 512;
 // ends at or below the window start takes the null-split exit, and the chunk
 // walk inside a split skips and masks exactly as the single-workgroup kernel
 // does, so the capacity independence holds with a window too.
-template <int D, bool ALIBI, bool WINDOW>
+template <int D, FlashVariant V>
 __global__ __launch_bounds__(256, 4) void flash_decode_split_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, float* __restrict__ part_m,
@@ -167,6 +170,8 @@ __global__ __launch_bounds__(256, 4) void flash_decode_split_kernel(
     int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss, int64_t v_sh,
     int H, int S, int Skv, float scale, int kv_group,
     const float* __restrict__ alibi_slopes, int window) {
+  constexpr bool ALIBI = V == FlashVariant::kAlibi,
+                 WINDOW = V == FlashVariant::kWindow;
   constexpr int DPL = D / 64;
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -320,6 +325,15 @@ __global__ __launch_bounds__(64, 8) void flash_decode_merge_kernel(
     *(uint16_t*)(op + t * 64 + lane) = f2bf(out[t] * inv);
 }
 
+// decode has no relative-position table and no packed documents (the binding
+// rejects window together with ALiBi): three of the five variants exist
+FlashVariant decode_variant(const float* alibi_slopes, int window) {
+  return flash_variant(alibi_slopes, window, nullptr, nullptr);
+}
+constexpr bool is_decode_variant(FlashVariant v) {
+  return v != FlashVariant::kRelBias && v != FlashVariant::kDocs;
+}
+
 }  // namespace
 
 extern "C" int flash_decode_num_splits(int B, int H, int Skv) {
@@ -338,26 +352,15 @@ extern "C" void flash_decode_bf16(const void* q, const void* k, const void* v,
                                   int H, int Skv, int D, float scale,
                                   int kv_group, const float* alibi_slopes,
                                   int window, hipStream_t stream) {
-  dim3 grid(B * H);
-#define DECODE_ARGS                                                            \
-  (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, kv_len,    \
-      q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, o_sb, o_sh, H, Skv,      \
-      scale, kv_group, alibi_slopes, window
-#define DECODE_LAUNCH(DD, AL, WIN) \
-  flash_decode_kernel<DD, AL, WIN><<<grid, dim3(256), 0, stream>>>(DECODE_ARGS)
-  // the binding rejects window together with ALiBi: no cross product
-  const bool alibi = alibi_slopes != nullptr;
-  if (D == 64) {
-    if (alibi) DECODE_LAUNCH(64, true, false);
-    else if (window > 0) DECODE_LAUNCH(64, false, true);
-    else DECODE_LAUNCH(64, false, false);
-  } else if (D == 128) {
-    if (alibi) DECODE_LAUNCH(128, true, false);
-    else if (window > 0) DECODE_LAUNCH(128, false, true);
-    else DECODE_LAUNCH(128, false, false);
-  }
-#undef DECODE_LAUNCH
-#undef DECODE_ARGS
+  const dim3 grid(B * H);
+  flash_dispatch(D, decode_variant(alibi_slopes, window), [&](auto dc, auto vc) {
+    if constexpr (is_decode_variant(decltype(vc)::value))
+      flash_decode_kernel<decltype(dc)::value, decltype(vc)::value>
+          <<<grid, dim3(256), 0, stream>>>(
+              (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o,
+              kv_len, q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, o_sb, o_sh, H,
+              Skv, scale, kv_group, alibi_slopes, window);
+  });
 }
 
 extern "C" void flash_decode_split_bf16(
@@ -367,28 +370,17 @@ extern "C" void flash_decode_split_bf16(
     int64_t v_ss, int64_t v_sh, int64_t o_sb, int64_t o_sh, int B, int H,
     int S, int Skv, int D, float scale, int kv_group, const float* alibi_slopes,
     int window, hipStream_t stream) {
-  dim3 grid(B * H * S), mgrid(B * H);
-#define SPLIT_ARGS                                                             \
-  (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, part_m, part_l,        \
-      part_acc, kv_len, q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, H, S,  \
-      Skv, scale, kv_group, alibi_slopes, window
-#define SPLIT_LAUNCH(DD, AL, WIN)                                              \
-  flash_decode_split_kernel<DD, AL, WIN><<<grid, dim3(256), 0, stream>>>(      \
-      SPLIT_ARGS)
-  const bool alibi = alibi_slopes != nullptr;
-  if (D == 64) {
-    if (alibi) SPLIT_LAUNCH(64, true, false);
-    else if (window > 0) SPLIT_LAUNCH(64, false, true);
-    else SPLIT_LAUNCH(64, false, false);
-    flash_decode_merge_kernel<64><<<mgrid, dim3(64), 0, stream>>>(
-        part_m, part_l, part_acc, (bf16_t*)o, H, S, o_sb, o_sh);
-  } else if (D == 128) {
-    if (alibi) SPLIT_LAUNCH(128, true, false);
-    else if (window > 0) SPLIT_LAUNCH(128, false, true);
-    else SPLIT_LAUNCH(128, false, false);
-    flash_decode_merge_kernel<128><<<mgrid, dim3(64), 0, stream>>>(
-        part_m, part_l, part_acc, (bf16_t*)o, H, S, o_sb, o_sh);
-  }
-#undef SPLIT_LAUNCH
-#undef SPLIT_ARGS
+  const dim3 grid(B * H * S), mgrid(B * H);
+  flash_dispatch(D, decode_variant(alibi_slopes, window), [&](auto dc, auto vc) {
+    if constexpr (is_decode_variant(decltype(vc)::value)) {
+      constexpr int DD = decltype(dc)::value;
+      flash_decode_split_kernel<DD, decltype(vc)::value>
+          <<<grid, dim3(256), 0, stream>>>(
+              (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, part_m, part_l,
+              part_acc, kv_len, q_sb, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, H, S,
+              Skv, scale, kv_group, alibi_slopes, window);
+      flash_decode_merge_kernel<DD><<<mgrid, dim3(64), 0, stream>>>(
+          part_m, part_l, part_acc, (bf16_t*)o, H, S, o_sb, o_sh);
+    }
+  });
 }

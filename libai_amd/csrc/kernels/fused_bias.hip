@@ -5,6 +5,7 @@
 // Memory-bound: 16-byte vectorized loads, fp32 math, hash-recomputed dropout
 // masks (no mask tensor traffic; backward regenerates the identical mask).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -16,6 +16,7 @@
 //   A-frag (lane i=l&31, k=(l>>5)*8+j) <- tr-read of the dY tile
 //   B-frag (lane j=l&31, same k split) <- tr-read of the X tile
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

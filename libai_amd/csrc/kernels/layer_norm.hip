@@ -6,6 +6,7 @@
 // mean/rstd cached for backward.  Weight grads use a two-stage column
 // reduction (partials over row-groups, then a fold) to avoid atomics.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -11,6 +11,7 @@
 #include <hip/hip_fp8.h>
 
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

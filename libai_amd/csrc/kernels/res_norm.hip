@@ -16,6 +16,7 @@
 // fold through LDS in wave order, and each block writes one partial row
 // (no float atomics: the result is the same from run to run).
 #include "common.h"
+#include "launchers.h"
 
 // Bit-identity with the separate kernels needs the same roundings, and which
 // products hipcc contracts into an fma there depends on the code around

@@ -11,6 +11,7 @@
 // y = silu(gate) * up with gate/up the two halves of one col-parallel
 // projection; backward recomputes silu from the saved input.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

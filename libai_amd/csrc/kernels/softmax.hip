@@ -14,6 +14,7 @@
 // replaces reference K14, libai/models/gpt_model.py:44-51); padding masks are
 // additive -10000 like the reference.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -41,6 +41,8 @@ Replaces the reference's K2-K5 chain (reference
 libai/layers/attention.py:211-253).
 """
 
+from typing import NamedTuple, Optional
+
 import torch
 
 from ._ext import draw_seed, ext
@@ -72,49 +74,75 @@ def bias_rel_table(position_bias):
     return getattr(position_bias, "_rel_bias_table", None)
 
 
-def _rel_bias_arg(rel_bias, alibi_slopes, window):
-    """Rejects a relative-position table together with ALiBi or a window."""
-    if rel_bias is None:
-        return None
-    if alibi_slopes is not None:
-        raise ValueError("rel_bias cannot be combined with alibi_slopes")
-    if window is not None and window != 0:
-        raise ValueError("rel_bias cannot be combined with a sliding window")
-    return rel_bias
+class _Variant(NamedTuple):
+    """The kernel variant arguments, in the order ``_C.flash_fwd`` and
+    ``_C.flash_bwd`` take them after ``kv_len``.  At most one variant is on."""
+
+    alibi_slopes: Optional[torch.Tensor] = None  # constant: no grad flows to it
+    window: int = 0                              # 0 = off
+    rel_bias: Optional[torch.Tensor] = None      # learned: the one with a grad
+    doc_start: Optional[torch.Tensor] = None     # int32: no grad flows to them
+    doc_end: Optional[torch.Tensor] = None
 
 
-def _doc_bounds_arg(doc_bounds, causal, alibi_slopes, window, rel_bias):
-    """(doc_start, doc_end) kernel arguments, (None, None) = off.  Rejects
-    document bounds together with anything they do not compose with."""
-    if doc_bounds is None:
-        return None, None
-    if not causal:
-        raise ValueError("doc_bounds requires causal attention")
-    if alibi_slopes is not None:
-        raise ValueError("doc_bounds cannot be combined with alibi_slopes")
-    if window is not None and window != 0:
-        raise ValueError("doc_bounds cannot be combined with a sliding window")
+def _variant_args(n_keys, causal=True, alibi_slopes=None, window=None, rel_bias=None,
+                  doc_bounds=None):
+    """Checks the variant arguments against each other and normalizes them: a
+    window of None or 0, or one that covers all n_keys keys (it masks nothing
+    and runs the windowless instantiation), is off."""
+    windowed = window is not None and window != 0
+    if doc_bounds is not None:
+        if not causal:
+            raise ValueError("doc_bounds requires causal attention")
+        if alibi_slopes is not None:
+            raise ValueError("doc_bounds cannot be combined with alibi_slopes")
+        if windowed:
+            raise ValueError("doc_bounds cannot be combined with a sliding window")
+        if rel_bias is not None:
+            raise ValueError("doc_bounds cannot be combined with rel_bias")
+        if doc_bounds[0] is None or doc_bounds[1] is None:
+            raise ValueError("doc_bounds needs both doc_start and doc_end")
     if rel_bias is not None:
-        raise ValueError("doc_bounds cannot be combined with rel_bias")
-    doc_start, doc_end = doc_bounds
-    if doc_start is None or doc_end is None:
-        raise ValueError("doc_bounds needs both doc_start and doc_end")
-    return doc_start, doc_end
+        if alibi_slopes is not None:
+            raise ValueError("rel_bias cannot be combined with alibi_slopes")
+        if windowed:
+            raise ValueError("rel_bias cannot be combined with a sliding window")
+    if windowed:
+        window = int(window)
+        if window < 0:
+            raise ValueError(f"window must be >= 1 (or None/0 for off), got {window}")
+        if not causal:
+            raise ValueError("a sliding window requires causal attention")
+        if alibi_slopes is not None:
+            raise ValueError("a sliding window cannot be combined with alibi_slopes")
+    doc_start, doc_end = doc_bounds if doc_bounds is not None else (None, None)
+    return _Variant(alibi_slopes, window if windowed and window < n_keys else 0,
+                    rel_bias, doc_start, doc_end)
 
 
-def _window_arg(window, n_keys, causal=True, alibi_slopes=None):
-    """Kernel argument for a sliding window: 0 = off.  A window that covers
-    all n_keys keys masks nothing and runs the windowless instantiation."""
-    if window is None or window == 0:
-        return 0
-    window = int(window)
-    if window < 0:
-        raise ValueError(f"window must be >= 1 (or None/0 for off), got {window}")
-    if not causal:
-        raise ValueError("a sliding window requires causal attention")
-    if alibi_slopes is not None:
-        raise ValueError("a sliding window cannot be combined with alibi_slopes")
-    return 0 if window >= n_keys else window
+def _save_variant(ctx, variant, *tensors):
+    """Saves the forward's tensors, the table included when there is one."""
+    has_rel_bias = variant.rel_bias is not None
+    ctx.save_for_backward(*tensors, *([variant.rel_bias] if has_rel_bias else []))
+    ctx.variant = variant._replace(rel_bias=None)  # the table lives in saved_tensors
+    ctx.has_rel_bias = has_rel_bias
+
+
+def _saved_variant(ctx):
+    """-> (the tensors given to _save_variant, the variant as it was saved)."""
+    saved = ctx.saved_tensors
+    if not ctx.has_rel_bias:
+        return saved, ctx.variant
+    return saved[:-1], ctx.variant._replace(rel_bias=saved[-1])
+
+
+def _variant_grads(ctx, first, grads):
+    """The backward's return values for the variant inputs, which start at
+    input `first`: the table's gradient (flash_bwd appends it to dq, dk, dv
+    when there is a table) where it is wanted, None everywhere else."""
+    at = first + _Variant._fields.index("rel_bias")
+    d_rel = grads[3] if ctx.has_rel_bias and ctx.needs_input_grad[at] else None
+    return tuple(_Variant(window=None, rel_bias=d_rel))
 
 
 def flash_attention_available(head_dim, dtype, device, sq, sk, pad_mask):
@@ -137,39 +165,29 @@ class _FlashAttnQKVFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, qkv5, scale, p_drop, causal, kv_len, alibi_slopes=None,
-                window=0, rel_bias=None, doc_start=None, doc_end=None):
+    def forward(ctx, qkv5, scale, p_drop, causal, kv_len, *variant):
         q = qkv5[..., 0, :]
         k = qkv5[..., 1, :]
         v = qkv5[..., 2, :]
         seed = draw_seed() if p_drop > 0 else 0
         o, lse = ext().flash_fwd(q, k, v, scale, p_drop, seed, causal, kv_len,
-                                 alibi_slopes, window, rel_bias, doc_start, doc_end)
-        if rel_bias is None:
-            ctx.save_for_backward(qkv5, o, lse)
-        else:
-            ctx.save_for_backward(qkv5, o, lse, rel_bias)
-        ctx.has_rel_bias = rel_bias is not None
+                                 *variant)
+        _save_variant(ctx, _Variant(*variant), qkv5, o, lse)
         ctx.kv_len = kv_len
-        ctx.alibi_slopes = alibi_slopes  # constant: no grad flows to it
-        ctx.window = window
-        ctx.doc_bounds = (doc_start, doc_end)  # int32: no grad flows to them
         ctx.meta = (scale, p_drop, seed, causal)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv5, o, lse, *rest = ctx.saved_tensors
-        rel_bias = rest[0] if ctx.has_rel_bias else None
+        (qkv5, o, lse), variant = _saved_variant(ctx)
         scale, p_drop, seed, causal = ctx.meta
         dqkv = torch.empty_like(qkv5)
         grads = ext().flash_bwd(
             qkv5[..., 0, :], qkv5[..., 1, :], qkv5[..., 2, :], o, do.contiguous(),
-            lse, scale, p_drop, seed, causal, dqkv, ctx.kv_len,
-            ctx.alibi_slopes, ctx.window, rel_bias, *ctx.doc_bounds,
+            lse, scale, p_drop, seed, causal, dqkv, ctx.kv_len, *variant,
         )
-        d_rel = grads[3] if rel_bias is not None and ctx.needs_input_grad[7] else None
-        return dqkv, None, None, None, None, None, None, d_rel, None, None
+        # inputs: qkv5, scale, p_drop, causal, kv_len, then the variant
+        return (dqkv, None, None, None, None) + _variant_grads(ctx, 5, grads)
 
 
 def flash_attention_qkv(qkv5, scale, p_drop=0.0, causal=True, training=True,
@@ -184,47 +202,35 @@ def flash_attention_qkv(qkv5, scale, p_drop=0.0, causal=True, training=True,
     scores; differentiable (not combinable with alibi_slopes or window).
     doc_bounds: optional (doc_start, doc_end), int32 [B, S] each — packed
     documents: query i sees key j iff doc_start[b, i] <= j <= i."""
-    doc_start, doc_end = _doc_bounds_arg(doc_bounds, causal, alibi_slopes, window,
-                                         rel_bias)
-    rel_bias = _rel_bias_arg(rel_bias, alibi_slopes, window)
-    window = _window_arg(window, qkv5.shape[1], causal, alibi_slopes)
+    variant = _variant_args(qkv5.shape[1], causal, alibi_slopes, window, rel_bias,
+                            doc_bounds)
     return _FlashAttnQKVFn.apply(qkv5, scale, p_drop if training else 0.0, causal,
-                                 kv_len, alibi_slopes, window, rel_bias,
-                                 doc_start, doc_end)
+                                 kv_len, *variant)
 
 
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, scale, p_drop, causal, kv_len, alibi_slopes=None,
-                window=0, rel_bias=None, doc_start=None, doc_end=None):
+    def forward(ctx, q, k, v, scale, p_drop, causal, kv_len, *variant):
         # q, k, v: [B, S, H, D] (may be strided views of the fused qkv buffer)
         seed = draw_seed() if p_drop > 0 else 0
         o, lse = ext().flash_fwd(q, k, v, scale, p_drop, seed, causal, kv_len,
-                                 alibi_slopes, window, rel_bias, doc_start, doc_end)
-        if rel_bias is None:
-            ctx.save_for_backward(q, k, v, o, lse)
-        else:
-            ctx.save_for_backward(q, k, v, o, lse, rel_bias)
-        ctx.has_rel_bias = rel_bias is not None
+                                 *variant)
+        _save_variant(ctx, _Variant(*variant), q, k, v, o, lse)
         ctx.kv_len = kv_len
-        ctx.alibi_slopes = alibi_slopes
-        ctx.window = window
-        ctx.doc_bounds = (doc_start, doc_end)  # int32: no grad flows to them
         ctx.meta = (scale, p_drop, seed, causal)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse, *rest = ctx.saved_tensors
-        rel_bias = rest[0] if ctx.has_rel_bias else None
+        (q, k, v, o, lse), variant = _saved_variant(ctx)
         scale, p_drop, seed, causal = ctx.meta
         grads = ext().flash_bwd(
             q, k, v, o, do.contiguous(), lse, scale, p_drop, seed, causal, None,
-            ctx.kv_len, ctx.alibi_slopes, ctx.window, rel_bias, *ctx.doc_bounds,
+            ctx.kv_len, *variant,
         )
+        # inputs: q, k, v, scale, p_drop, causal, kv_len, then the variant
         dq, dk, dv = grads[:3]
-        d_rel = grads[3] if rel_bias is not None and ctx.needs_input_grad[9] else None
-        return dq, dk, dv, None, None, None, None, None, None, d_rel, None, None
+        return (dq, dk, dv, None, None, None, None) + _variant_grads(ctx, 7, grads)
 
 
 def flash_attention(q, k, v, scale, p_drop=0.0, causal=True, training=True,
@@ -242,13 +248,10 @@ def flash_attention(q, k, v, scale, p_drop=0.0, causal=True, training=True,
     documents: causal attention that stays inside the query's own document
     (needs Sq == Sk; not combinable with alibi_slopes, window, rel_bias or
     causal=False)."""
-    doc_start, doc_end = _doc_bounds_arg(doc_bounds, causal, alibi_slopes, window,
-                                         rel_bias)
-    rel_bias = _rel_bias_arg(rel_bias, alibi_slopes, window)
-    window = _window_arg(window, k.shape[1], causal, alibi_slopes)
+    variant = _variant_args(k.shape[1], causal, alibi_slopes, window, rel_bias,
+                            doc_bounds)
     return _FlashAttnFn.apply(q, k, v, scale, p_drop if training else 0.0, causal,
-                              kv_len, alibi_slopes, window, rel_bias, doc_start,
-                              doc_end)
+                              kv_len, *variant)
 
 
 def decode_attention_available(q, head_dim):
@@ -274,5 +277,6 @@ def flash_decode_attn(q, k, v, scale, kv_len=None, alibi_slopes=None,
     query at the last valid key, qpos = kv_len[b] - 1 (Skv - 1 if no kv_len).
     window: optional int W — only the last W valid keys are visible (and read):
     [max(0, kv_len[b] - W), kv_len[b])."""
-    window = _window_arg(window, k.shape[2], True, alibi_slopes)
-    return ext().flash_decode(q, k, v, scale, kv_len, alibi_slopes, window)
+    variant = _variant_args(k.shape[2], True, alibi_slopes, window)
+    return ext().flash_decode(q, k, v, scale, kv_len, variant.alibi_slopes,
+                              variant.window)
