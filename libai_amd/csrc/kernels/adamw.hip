@@ -27,11 +27,46 @@ struct AdamChunkDesc {
   int64_t n;       // number of elements in this chunk
 };
 
+struct AdamHyper {
+  float lr, beta1, beta2, eps, wd, inv_bc1, inv_bc2, grad_scale;
+  float omb1, omb2;  // 1 - beta1, 1 - beta2
+};
+
+// One parameter element.  Shared by the vector and the scalar loop, with the
+// contractions written out, so that where a parameter sits in its bucket
+// (which decides the loop) cannot decide a bit.  The two moment updates are
+// contracted the other way round in the two instantiations: that is what the
+// compiler made of `beta * m + (1 - beta) * g` in the scalar kernel this one
+// replaces, read from that kernel's ISA, so that optimizer states written by
+// it should continue bit for bit.  No fixture pins that: the tests compare
+// the two loops of this kernel with each other, not with the old one.
+template <class E>
+__device__ __forceinline__ void adamw_elem(float g, float& p, float& m, float& v,
+                                           const AdamHyper& h) {
+#pragma clang fp contract(off)
+  const float gv = g * h.grad_scale;
+  const float t = h.omb2 * gv;
+  if constexpr (std::is_same<E, BF16Elem>::value) {
+    m = fmaf(h.beta1, m, h.omb1 * gv);
+    v = fmaf(h.beta2, v, gv * t);
+  } else {
+    m = fmaf(h.omb1, gv, h.beta1 * m);
+    v = fmaf(gv, t, h.beta2 * v);
+  }
+  const float mhat = m * h.inv_bc1;
+  const float vhat = v * h.inv_bc2;
+  p = fmaf(-h.lr, fmaf(h.wd, p, mhat / (sqrtf(vhat) + h.eps)), p);
+}
+
+constexpr int AVEC = 8;  // elements per thread and iteration of the vector loops
+
 template <class E>
 __global__ void adamw_kernel(const AdamChunkDesc* __restrict__ chunks, float lr,
                              float beta1, float beta2, float eps, float wd,
                              float bc1, float bc2,  // 1-b1^t, 1-b2^t
                              float grad_scale) {
+  using VecT = typename E::VecT;
+  constexpr int GV = AVEC / E::VEC;  // 16-byte vectors of E per AVEC elements
   const AdamChunkDesc c = chunks[blockIdx.x];
   const int64_t n = c.n;
   typename E::T* p16 = (typename E::T*)c.param;
@@ -39,16 +74,58 @@ __global__ void adamw_kernel(const AdamChunkDesc* __restrict__ chunks, float lr,
   const typename E::T* g = (const typename E::T*)c.grad;
   float* m = (float*)c.m;
   float* v = (float*)c.v;
-  const float inv_bc1 = 1.0f / bc1, inv_bc2 = 1.0f / bc2;
+  const AdamHyper h = {lr,          beta1,       beta2,      eps,
+                       wd,          1.0f / bc1,  1.0f / bc2, grad_scale,
+                       1.0f - beta1, 1.0f - beta2};
 
-  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
-    float gv = E::to_f(g[i]) * grad_scale;
-    float pv = master[i];
-    float mv = m[i] = beta1 * m[i] + (1.0f - beta1) * gv;
-    float vv = v[i] = beta2 * v[i] + (1.0f - beta2) * gv * gv;
-    float mhat = mv * inv_bc1;
-    float vhat = vv * inv_bc2;
-    pv -= lr * (mhat / (sqrtf(vhat) + eps) + wd * pv);
+  // Parameters are views into flat buckets at any element offset: the
+  // 16-byte path serves a chunk only if all five of its pointers allow it
+  // (uniform over the block, which serves one chunk).  A null param
+  // (fp32-native) counts as aligned.
+  const bool aligned = ((c.param | c.master | c.grad | c.m | c.v) & 15) == 0;
+  const int64_t nvec = aligned ? n - n % AVEC : 0;
+
+  for (int64_t i = (int64_t)threadIdx.x * AVEC; i < nvec;
+       i += (int64_t)blockDim.x * AVEC) {
+    // all loads of the iteration first: 112 (bf16) / 128 bytes per lane in flight
+    VecT vg[GV];
+    f32x4 vp[2], vm[2], vv[2];
+#pragma unroll
+    for (int k = 0; k < GV; ++k) vg[k] = ((const VecT*)(g + i))[k];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      vp[k] = ((const f32x4*)(master + i))[k];
+      vm[k] = ((const f32x4*)(m + i))[k];
+      vv[k] = ((const f32x4*)(v + i))[k];
+    }
+    VecT o[GV];
+#pragma unroll
+    for (int j = 0; j < AVEC; ++j) {
+      float pv = vp[j / 4][j % 4], mv = vm[j / 4][j % 4], sv = vv[j / 4][j % 4];
+      adamw_elem<E>(E::to_f(vg[j / E::VEC][j % E::VEC]), pv, mv, sv, h);
+      vp[j / 4][j % 4] = pv;
+      vm[j / 4][j % 4] = mv;
+      vv[j / 4][j % 4] = sv;
+      o[j / E::VEC][j % E::VEC] = E::from_f(pv);
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      ((f32x4*)(m + i))[k] = vm[k];
+      ((f32x4*)(v + i))[k] = vv[k];
+      ((f32x4*)(master + i))[k] = vp[k];
+    }
+    if (p16) {
+#pragma unroll
+      for (int k = 0; k < GV; ++k) ((VecT*)(p16 + i))[k] = o[k];
+    }
+  }
+
+  // unaligned chunks, and the tail shorter than a vector
+  for (int64_t i = nvec + threadIdx.x; i < n; i += blockDim.x) {
+    float pv = master[i], mv = m[i], sv = v[i];
+    adamw_elem<E>(E::to_f(g[i]), pv, mv, sv, h);
+    m[i] = mv;
+    v[i] = sv;
     master[i] = pv;
     if (p16) p16[i] = E::from_f(pv);
   }
@@ -65,8 +142,22 @@ __global__ void l2norm_sq_kernel(const NormChunkDesc* __restrict__ chunks,
   __shared__ float red[16];
   const NormChunkDesc c = chunks[blockIdx.x];
   const typename E::T* x = (const typename E::T*)c.ptr;
+  using VecT = typename E::VecT;
+  constexpr int V = E::VEC;
   float s = 0.f;
-  for (int64_t i = threadIdx.x; i < c.n; i += blockDim.x) {
+  // 16-byte loads where the chunk's pointer allows them (see adamw_kernel);
+  // the loads of the unrolled iterations do not depend on each other
+  const int64_t nvec = (c.ptr & 15) == 0 ? c.n - c.n % V : 0;
+#pragma unroll 4
+  for (int64_t i = (int64_t)threadIdx.x * V; i < nvec; i += (int64_t)blockDim.x * V) {
+    const VecT vx = *(const VecT*)(x + i);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      float v = E::to_f(vx[j]);
+      s += v * v;
+    }
+  }
+  for (int64_t i = nvec + threadIdx.x; i < c.n; i += blockDim.x) {
     float v = E::to_f(x[i]);
     s += v * v;
   }

@@ -21,17 +21,17 @@ __device__ __forceinline__ float bf2f(uint16_t h) {
   return v.f;
 }
 
+// Round-to-nearest-even in hardware: gfx950 has v_cvt_pk_bf16_f32, half an
+// instruction per value where two casts feed neighbouring lanes of a vector
+// (the compiler pairs them), against ~6 VALU for the rounding by bit
+// manipulation.  Same bits for every finite and infinite input (tested over
+// all bf16 neighbourhoods, tests/gpu/test_elementwise_bits_gpu.py); a NaN
+// stays a NaN (quieted).  By the instruction's definition that holds for a
+// NaN whose payload sits only in the low 16 bits too, which the bit
+// manipulation could turn into an infinity; no kernel input reaches that
+// case from bf16 data, and no test covers it.
 __device__ __forceinline__ uint16_t f2bf(float f) {
-  union {
-    float f;
-    uint32_t u;
-  } v;
-  v.f = f;
-  // round-to-nearest-even
-  uint32_t lsb = (v.u >> 16) & 1u;
-  uint32_t rounded = v.u + 0x7fffu + lsb;
-  if ((v.u & 0x7f800000u) == 0x7f800000u) rounded = v.u;  // inf/nan passthrough
-  return (uint16_t)(rounded >> 16);
+  return __builtin_bit_cast(uint16_t, (__bf16)f);
 }
 
 // 8 x bf16 = one 16-byte load (the coalescing sweet spot per guide G13)
@@ -194,26 +194,52 @@ __device__ __forceinline__ uint32_t drop_threshold_u32(float p) {
 // fast erf (Abramowitz & Stegun 7.1.26, |err| <= 1.5e-7): ocml's erff is a
 // long polynomial and made the fused bias-gelu pass VALU-bound instead of
 // HBM-bound.
+//
+// The three functions below pin every contraction (contract(off) + explicit
+// fmaf): their outputs are recorded bit for bit in tests/golden/bias_gelu_*,
+// and which products the compiler would contract is its per-instantiation
+// choice (profiles/elementwise_valu.md).
+
+// 1 / d for d in [1, 2^96): the quotient of the IEEE division 1.0f / d, by the
+// same steps (v_rcp_f32, then the refinement fmas in the compiler's order),
+// without what that range never needs: both v_div_scale_f32 (they scale by 1
+// there), the scaling path of v_div_fmas_f32 and v_div_fixup_f32.
+__device__ __forceinline__ float rcp_ge1(float d) {
+#pragma clang fp contract(off)
+  float r = __builtin_amdgcn_rcpf(d);
+  r = fmaf(fmaf(-d, r, 1.0f), r, r);
+  float q = r;  // numerator 1.0f * r
+  q = fmaf(fmaf(-d, q, 1.0f), r, q);
+  return fmaf(fmaf(-d, q, 1.0f), r, q);
+}
+
 __device__ __forceinline__ float fast_erff(float x) {
+#pragma clang fp contract(off)
   const float a1 = 0.254829592f, a2 = -0.284496736f, a3 = 1.421413741f;
   const float a4 = -1.453152027f, a5 = 1.061405429f, p = 0.3275911f;
   float ax = fabsf(x);
-  float t = 1.0f / fmaf(p, ax, 1.0f);
+  // from ax ~ 2^97 on exp(-ax^2) is an exact 0 and t only has to be finite;
+  // the clamp keeps it so for ax = inf too (rcp_ge1(inf) would be a NaN)
+  float t = rcp_ge1(fminf(fmaf(p, ax, 1.0f), 0x1p+96f));
   float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, a5, a4), a3), a2), a1);
-  float y = 1.0f - poly * __expf(-ax * ax);
+  float y = fmaf(-__expf(-ax * ax), poly, 1.0f);
   return copysignf(y, x);
 }
 
 __device__ __forceinline__ float gelu_erf(float x) {
+#pragma clang fp contract(off)
   return 0.5f * x * (1.0f + fast_erff(x * 0.70710678118654752440f));
 }
 
-__device__ __forceinline__ float gelu_erf_grad(float x) {
+// `fused`: form cdf + x * pdf with one rounding (fma) or two.  The callers
+// pass what the recorded bits were made with, see bias_gelu_kernel.
+__device__ __forceinline__ float gelu_erf_grad(float x, bool fused = true) {
+#pragma clang fp contract(off)
   const float kInvSqrt2 = 0.70710678118654752440f;
   const float kInvSqrt2Pi = 0.3989422804014327f;
   float cdf = 0.5f * (1.0f + fast_erff(x * kInvSqrt2));
   float pdf = kInvSqrt2Pi * __expf(-0.5f * x * x);
-  return cdf + x * pdf;
+  return fused ? fmaf(x, pdf, cdf) : cdf + x * pdf;
 }
 
 #define CDIV(a, b) (((a) + (b)-1) / (b))

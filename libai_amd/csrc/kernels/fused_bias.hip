@@ -2,8 +2,11 @@
 //
 // Replaces the reference's flow._C.fused_bias_add_gelu (libai/layers/mlp.py:95-97)
 // and flow._C.fused_bias_add_dropout (mlp.py:104-106, attention.py:265-267).
-// Memory-bound: 16-byte vectorized loads, fp32 math, hash-recomputed dropout
-// masks (no mask tensor traffic; backward regenerates the identical mask).
+// 16-byte vectorized loads, fp32 math, hash-recomputed dropout masks (no mask
+// tensor traffic; backward regenerates the identical mask).  The
+// bias+dropout+residual kernels stream at 5.7-5.8 TB/s; the bias-gelu kernels
+// do not (4.6-4.8 TB/s at [49152, 4096]); their limiter is not identified,
+// see profiles/elementwise_valu.md for what was measured.
 #include "common.h"
 #include "launchers.h"
 
@@ -15,6 +18,39 @@ namespace {
 // 2D launch: thread owns ONE vector-column (bias loaded once, no per-element
 // modulo -- a flat grid-stride variant spent ~30 of its 406 loop instructions
 // on the emulated 64-bit `i % wvec`), rows strided by gridDim.y.
+//
+// The outputs are pinned bit for bit by tests/golden/bias_gelu_* (recorded
+// before the division and the bf16 round were rewritten), so every
+// contraction is written out.  Two of them look arbitrary and are what the
+// compiler chose for the earlier source, in the bf16 and the fp32
+// instantiation alike: the last two elements of a vector form cdf + x * pdf
+// with a rounded product, the others with an fma; and the bias gradient adds
+// the unrounded product dy * gelu'(x), not the rounded dx.
+
+// one vector: out = gelu(x + b), or dy * gelu'(x + b) with db += the same
+template <class E, bool GRAD>
+__device__ __forceinline__ typename E::VecT bias_gelu_vec(typename E::VecT vx,
+                                                          typename E::VecT vdy,
+                                                          const float* fb,
+                                                          float* db) {
+#pragma clang fp contract(off)
+  constexpr int V = E::VEC;
+  typename E::VecT o;
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    const float xv = E::to_f(vx[j]) + fb[j];
+    if (GRAD) {
+      const float d = gelu_erf_grad(xv, /*fused=*/j < V - 2);
+      const float dyv = E::to_f(vdy[j]);
+      o[j] = E::from_f(dyv * d);
+      db[j] = fmaf(d, dyv, db[j]);  // bias grad rides along: no second pass over dx
+    } else {
+      o[j] = E::from_f(gelu_erf(xv));
+    }
+  }
+  return o;
+}
+
 template <class E, bool GRAD>
 __global__ void bias_gelu_kernel(const typename E::T* __restrict__ x,
                                  const typename E::T* __restrict__ b,
@@ -28,30 +64,29 @@ __global__ void bias_gelu_kernel(const typename E::T* __restrict__ x,
   const int64_t R = n / W;
   const int cv = blockIdx.x * blockDim.x + threadIdx.x;
   if (cv >= wvec) return;
-  VecT vb;
-  if (b) vb = ((const VecT*)b)[cv];
+  float fb[V];
+  {
+    VecT vb;
+    if (b) vb = ((const VecT*)b)[cv];
+#pragma unroll
+    for (int j = 0; j < V; ++j) fb[j] = b ? E::to_f(vb[j]) : 0.f;
+  }
   float db[GRAD ? V : 1] = {0.f};
+  const VecT* xp = (const VecT*)x + cv;
+  VecT* op = (VecT*)out + cv;
+  // dy of the vector at i (forward: there is none, and nothing reads it)
+  auto load_dy = [&](int64_t i) {
+    VecT d = {};
+    if constexpr (GRAD) d = ((const VecT*)dy)[i + cv];
+    return d;
+  };
+  // One row per iteration.  Two rows with all loads first measured the same
+  // per call (profiles/elementwise_valu.md) at three times the code and 5-6
+  // instead of 7-8 waves per SIMD, so it is not built.
   for (int64_t r = blockIdx.y; r < R; r += gridDim.y) {
-    const int64_t i = r * wvec + cv;
-    VecT vx = ((const VecT*)x)[i];
-    VecT o;
-    if (GRAD) {
-      VecT vdy = ((const VecT*)dy)[i];
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        float xv = E::to_f(vx[j]) + (b ? E::to_f(vb[j]) : 0.f);
-        float g = E::to_f(vdy[j]) * gelu_erf_grad(xv);
-        o[j] = E::from_f(g);
-        db[j] += g;  // bias grad rides along: no second pass over dx
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        float xv = E::to_f(vx[j]) + (b ? E::to_f(vb[j]) : 0.f);
-        o[j] = E::from_f(gelu_erf(xv));
-      }
-    }
-    ((VecT*)out)[i] = o;
+    const int64_t i = r * wvec;
+    const VecT vx = xp[i];
+    op[i] = bias_gelu_vec<E, GRAD>(vx, load_dy(i), fb, db);
   }
   if (GRAD && db_partial != nullptr) {
 #pragma unroll
