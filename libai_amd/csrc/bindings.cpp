@@ -467,8 +467,20 @@ static VariantPtrs variant_ptrs(const char* op, const torch::Tensor& q, int64_t 
                                 const OptTensor& alibi_slopes, int64_t window,
                                 const OptTensor& rel_bias = c10::nullopt,
                                 const OptTensor& doc_start = c10::nullopt,
-                                const OptTensor& doc_end = c10::nullopt) {
+                                const OptTensor& doc_end = c10::nullopt,
+                                int64_t q_offset = 0) {
   VariantPtrs p;
+  // query offset (flash_fwd only): query row i sits at key position
+  // q_offset + i.  0 is off and keeps the top-left alignment for Sq != Sk.
+  TORCH_CHECK(q_offset >= 0, op, ": q_offset must be >= 0");
+  if (q_offset > 0) {
+    TORCH_CHECK(causal, op, ": q_offset requires causal attention");
+    TORCH_CHECK(q_offset + Sq <= Sk, op, ": q_offset + Sq must not exceed Sk");
+    TORCH_CHECK(!rel_bias.has_value(), op,
+                ": q_offset cannot be combined with rel_bias");
+    TORCH_CHECK(!doc_start.has_value() && !doc_end.has_value(), op,
+                ": q_offset cannot be combined with document bounds");
+  }
   auto on_q_device = [&](const torch::Tensor& t, torch::ScalarType dtype) {
     return t.scalar_type() == dtype && t.is_cuda() &&
            t.get_device() == q.get_device() && t.is_contiguous();
@@ -486,7 +498,8 @@ static VariantPtrs variant_ptrs(const char* op, const torch::Tensor& q, int64_t 
     TORCH_CHECK(causal, op, ": a sliding window requires causal attention");
     TORCH_CHECK(!has_alibi, op,
                 ": a sliding window cannot be combined with alibi_slopes");
-    TORCH_CHECK(Sq == Sk, op, ": a sliding window needs Sq == Sk");
+    // with an offset every query position lies inside the keys (checked above)
+    TORCH_CHECK(q_offset > 0 || Sq == Sk, op, ": a sliding window needs Sq == Sk");
     p.window = (int)std::min<int64_t>(window, std::max<int64_t>(Sk, 1));
   }
   if (rel_bias.has_value()) {
@@ -664,7 +677,8 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
                                                    int64_t window,
                                                    c10::optional<torch::Tensor> rel_bias,
                                                    c10::optional<torch::Tensor> doc_start,
-                                                   c10::optional<torch::Tensor> doc_end) {
+                                                   c10::optional<torch::Tensor> doc_end,
+                                                   int64_t q_offset) {
   const int* kvl = kv_len_ptr(kv_len, q.size(0), /*contiguous=*/true);
   // q/k/v: [B, S, H, D] (strided views into a fused qkv buffer are fine; the
   // last dim must be contiguous and 16B-aligned)
@@ -675,16 +689,23 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
             D = (int)q.size(3);
   const int Sk = (int)k.size(1), Hkv = (int)k.size(2);
   TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
-  TORCH_CHECK(Sk % 8 == 0, "Sk must be a multiple of 8");
+  // the dropout hash keys on Sk / 4 and the backward stages keys in runs of
+  // 8; a forward without dropout bounds every staged key row by Sk, so a
+  // ragged key count (a cache of 117 keys) is fine there
+  TORCH_CHECK(p_drop == 0.0 || Sk % 8 == 0,
+              "Sk must be a multiple of 8 (with dropout)");
   TORCH_CHECK(Hkv > 0 && H % Hkv == 0 && (int)v.size(2) == Hkv,
               "GQA head counts: H divisible by Hkv, v matches k");
+  TORCH_CHECK(q_offset == 0 || p_drop == 0.0,
+              "flash_fwd: q_offset cannot be combined with dropout");
   const VariantPtrs var = variant_ptrs("flash_fwd", q, B, H, Sq, Sk, causal,
                                        alibi_slopes, window, rel_bias, doc_start,
-                                       doc_end);
+                                       doc_end, q_offset);
   auto o = torch::empty({B, Sq, H, D}, q.options());
   auto lse = torch::empty({B, H, Sq}, q.options().dtype(torch::kFloat32));
-  const FlashFwdArgs a =
+  FlashFwdArgs a =
       flash_args(q, k, v, o, lse, kvl, scale, p_drop, seed, causal, var);
+  a.q_off = (int)q_offset;
   flash_fwd_bf16(a, cur_stream());
   check_launch("flash_fwd");
   return {o, lse};
@@ -699,11 +720,13 @@ py::tuple flash_bwd(
     c10::optional<torch::Tensor> kv_len,
     c10::optional<torch::Tensor> alibi_slopes, int64_t window,
     c10::optional<torch::Tensor> rel_bias, c10::optional<torch::Tensor> doc_start,
-    c10::optional<torch::Tensor> doc_end) {
+    c10::optional<torch::Tensor> doc_end, c10::optional<torch::Tensor> dkv) {
   const int* kvl = kv_len_ptr(kv_len, q.size(0), /*contiguous=*/true);
   const int B = (int)q.size(0), Sq = (int)q.size(1), H = (int)q.size(2),
             D = (int)q.size(3);
   const int Sk = (int)k.size(1), Hkv = (int)k.size(2);
+  // the forward waives this without dropout; the backward kernels do not
+  TORCH_CHECK(Sk % 8 == 0, "flash_bwd: Sk must be a multiple of 8");
   const VariantPtrs var = variant_ptrs("flash_bwd", q, B, H, Sq, Sk, causal,
                                        alibi_slopes, window, rel_bias, doc_start,
                                        doc_end);
@@ -719,6 +742,19 @@ py::tuple flash_bwd(
     dq = g.select(3, 0);
     dk = g.select(3, 1);
     dv = g.select(3, 2);
+    TORCH_CHECK(!dkv.has_value(), "flash_bwd: dqkv and dkv exclude each other");
+  } else if (dkv.has_value()) {
+    // [B, Sk, Hkv, 2, D] fused grad buffer of a packed key/value projection
+    // (cross-attention): write the k/v grads in place
+    auto g = dkv.value();
+    TORCH_CHECK(g.dim() == 5 && g.size(0) == B && g.size(1) == Sk &&
+                    g.size(2) == Hkv && g.size(3) == 2 && g.size(4) == D &&
+                    g.stride(4) == 1 && g.scalar_type() == q.scalar_type() &&
+                    g.is_cuda() && g.get_device() == q.get_device(),
+                "flash_bwd: dkv must be [B, Sk, Hkv, 2, D] of q's dtype and device");
+    dq = torch::empty_like(q, q.options());
+    dk = g.select(3, 0);
+    dv = g.select(3, 1);
   } else {
     dq = torch::empty_like(q, q.options());
     dk = torch::empty({B, Sk, Hkv, D}, q.options());
@@ -929,13 +965,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"), py::arg("p_drop"), py::arg("seed"), py::arg("causal"),
         py::arg("kv_len"), py::arg("alibi_slopes") = py::none(), py::arg("window") = 0,
         py::arg("rel_bias") = py::none(), py::arg("doc_start") = py::none(),
-        py::arg("doc_end") = py::none());
+        py::arg("doc_end") = py::none(), py::arg("q_offset") = 0);
   m.def("flash_bwd", &flash_bwd, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o"), py::arg("dout"), py::arg("lse"), py::arg("scale"),
         py::arg("p_drop"), py::arg("seed"), py::arg("causal"), py::arg("dqkv"),
         py::arg("kv_len"), py::arg("alibi_slopes") = py::none(), py::arg("window") = 0,
         py::arg("rel_bias") = py::none(), py::arg("doc_start") = py::none(),
-        py::arg("doc_end") = py::none());
+        py::arg("doc_end") = py::none(), py::arg("dkv") = py::none());
   m.def("attn_dropout_apply", &attn_dropout_apply);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);

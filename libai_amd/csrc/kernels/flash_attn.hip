@@ -310,7 +310,15 @@ __device__ __forceinline__ void relb_flush(float* ring, float* __restrict__ grow
   }
 }
 
-template <int D, FlashVariant V>
+// OFFS: compile-time switch for a query chunk behind cached keys (inference,
+// forward only): query row i of the call sits at key position q_off + i, so
+// the causal mask, the window band and the ALiBi distance are taken at
+// q_off + i while loads, stores and lse keep the row index i.  q_off = Sk - Sq
+// is the bottom-right alignment a cat([past, new]) cache needs.  Instantiated
+// for the plain, ALiBi and window variants; every use of q_off sits under
+// `if constexpr (OFFS)` (at_pos below), so the OFFS=false instantiations keep
+// their instruction streams and keep the top-left alignment for Sq != Sk.
+template <int D, FlashVariant V, bool OFFS = false>
 __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
     const bf16_t* __restrict__ v, bf16_t* __restrict__ o, float* __restrict__ lse,
@@ -319,12 +327,20 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     int64_t v_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh, int H, int Sq, int Sk,
     float scale, float p_drop, uint64_t seed, int causal, int kv_group,
     const float* __restrict__ alibi_slopes, int window,
-    const float* __restrict__ rel_bias, const int* __restrict__ doc_start) {
+    const float* __restrict__ rel_bias, const int* __restrict__ doc_start,
+    int q_off) {
   constexpr bool ALIBI = V == FlashVariant::kAlibi,
                  WINDOW = V == FlashVariant::kWindow,
                  RELB = V == FlashVariant::kRelBias, DOCS = V == FlashVariant::kDocs;
+  static_assert(!OFFS || !(RELB || DOCS), "no query offset for rel_bias / documents");
   constexpr int DT = D / 32;
   constexpr int KC = D / 16;
+  // key position of query row `row` (q_off is a kernel argument: adding it
+  // keeps a wave-uniform row wave-uniform)
+  auto at_pos = [&](int row) {
+    if constexpr (OFFS) return row + q_off;
+    else return row;
+  };
 
   // 2 x KVB rows staged per barrier round: halves barrier count per unit of
   // compute (PMC: 43% of forward wave cycles were barrier/wait-parked)
@@ -378,10 +394,14 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
   // per-sequence valid length; replaces the reference's additive -10000 pad
   // mask, attention.py:221-226)
   const int sk_eff = (kv_len != nullptr) ? kv_len[b] : Sk;
-  const int kv_end = causal ? min(sk_eff, q_block + QBLK) : sk_eff;
+  // positions of the block's first row, the wave's first row and the lane's
+  // row: what the masks compare keys with (the rows themselves without OFFS)
+  const int p_block = at_pos(q_block), p_base = at_pos(q_base);
+  const int kv_end = causal ? min(sk_eff, p_block + QBLK) : sk_eff;
   const int n_rounds = CDIV(kv_end, 2 * KVB);
   const float ks = (p_drop > 0.f) ? 1.0f / (1.0f - p_drop) : 1.0f;
   const int qg = q_base + l31;
+  const int pg = at_pos(qg);
   // scores live in the exp2 domain, so the slope is pre-multiplied by log2e
   float slope2 = 0.f;
   if constexpr (ALIBI) slope2 = alibi_slopes[h] * 1.4426950408889634f;
@@ -389,7 +409,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
   // sliding window: the first staging round is the one holding the lowest
   // key any query of this block can see (uniform across the workgroup)
   int round0 = 0;
-  if constexpr (WINDOW) round0 = max(0, q_block - window + 1) / (2 * KVB);
+  if constexpr (WINDOW) round0 = max(0, p_block - window + 1) / (2 * KVB);
   // packed documents: lane's lower bound; the block's lowest bound (its first
   // query's: doc_start is non-decreasing) picks the first staging round, the
   // wave's first and last queries give the sub-tile skip and the tile class
@@ -425,9 +445,9 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     for (int sub = 0; sub < 2; ++sub) {
     const int kv0 = kvR + sub * KVB;
     const int ro = sub * KVB;  // row offset inside the staged images
-    if (kv0 >= kv_end || (causal && kv0 > q_base + QB - 1)) continue;
+    if (kv0 >= kv_end || (causal && kv0 > p_base + QB - 1)) continue;
     if constexpr (WINDOW) {  // sub-tile entirely below this wave's band
-      if (kv0 + KVB - 1 < q_base - window + 1) continue;
+      if (kv0 + KVB - 1 < p_base - window + 1) continue;
     }
     if constexpr (DOCS) {  // sub-tile entirely before this wave's documents
       if (kv0 + KVB - 1 < doc_lo_w) continue;
@@ -452,8 +472,8 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
     // its lowest q >= its highest kv, under WINDOW its farthest pair inside
     // the band -- and runs the body without compares, selects or sentinels.
     bool interior = kv0 + KVB <= sk_eff && q_base + QB <= Sq &&
-                    (!causal || q_base >= kv0 + KVB - 1);
-    if constexpr (WINDOW) interior = interior && (q_base + QB - 1 - kv0 < window);
+                    (!causal || p_base >= kv0 + KVB - 1);
+    if constexpr (WINDOW) interior = interior && (p_base + QB - 1 - kv0 < window);
     if constexpr (DOCS) interior = interior && (kv0 >= doc_lo_top);
     auto softmax_tile = [&](auto masked_c) {
       constexpr bool MASKED = decltype(masked_c)::value;
@@ -461,7 +481,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
       // kv - q of this lane's first score; the per-register offsets below are
       // compile-time constants (exact in fp32)
       float rel0 = 0.f;
-      if constexpr (ALIBI) rel0 = (float)(kv0 + 4 * hi - qg);
+      if constexpr (ALIBI) rel0 = (float)(kv0 + 4 * hi - pg);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         int kva = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
@@ -478,11 +498,11 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
           bb += rb_lds[e + 32];
         }
         if constexpr (MASKED) {
-          if (kva >= sk_eff || (causal && kva > qg)) a = -3.0e38f;
-          if (kvb >= sk_eff || (causal && kvb > qg)) bb = -3.0e38f;
+          if (kva >= sk_eff || (causal && kva > pg)) a = -3.0e38f;
+          if (kvb >= sk_eff || (causal && kvb > pg)) bb = -3.0e38f;
           if constexpr (WINDOW) {
-            if (qg - kva >= window) a = -3.0e38f;
-            if (qg - kvb >= window) bb = -3.0e38f;
+            if (pg - kva >= window) a = -3.0e38f;
+            if (pg - kvb >= window) bb = -3.0e38f;
           }
           if constexpr (DOCS) {
             if (kva < doc_lo) a = -3.0e38f;
@@ -1376,15 +1396,29 @@ extern "C" void flash_fwd_bf16(const FlashFwdArgs& a, hipStream_t stream) {
   const FlashVariant variant =
       flash_variant(a.alibi_slopes, window, a.rel_bias, a.doc_start);
   flash_dispatch(a.D, variant, [&](auto dc, auto vc) {
-    flash_fwd_kernel<decltype(dc)::value, decltype(vc)::value>
-        <<<grid, block, 0, stream>>>(
-            in(a.q), in(a.k), in(a.v), out(a.o), a.lse, a.kv_len,
-            a.q.sb, a.q.ss, a.q.sh,
-            a.k.sb, a.k.ss, a.k.sh,
-            a.v.sb, a.v.ss, a.v.sh,
-            a.o.sb, a.o.ss, a.o.sh,
-            a.H, a.Sq, a.Sk, a.scale, a.p_drop, a.seed, a.causal, a.kv_group,
-            a.alibi_slopes, window, a.rel_bias, a.doc_start);
+    constexpr int DD = decltype(dc)::value;
+    constexpr FlashVariant VV = decltype(vc)::value;
+    auto launch = [&](auto offs) {
+      flash_fwd_kernel<DD, VV, decltype(offs)::value>
+          <<<grid, block, 0, stream>>>(
+              in(a.q), in(a.k), in(a.v), out(a.o), a.lse, a.kv_len,
+              a.q.sb, a.q.ss, a.q.sh,
+              a.k.sb, a.k.ss, a.k.sh,
+              a.v.sb, a.v.ss, a.v.sh,
+              a.o.sb, a.o.ss, a.o.sh,
+              a.H, a.Sq, a.Sk, a.scale, a.p_drop, a.seed, a.causal, a.kv_group,
+              a.alibi_slopes, window, a.rel_bias, a.doc_start, a.q_off);
+    };
+    // the offset instantiations exist for plain, ALiBi and window only (the
+    // binding rejects an offset with the other two)
+    if constexpr (VV == FlashVariant::kPlain || VV == FlashVariant::kAlibi ||
+                  VV == FlashVariant::kWindow) {
+      if (a.q_off > 0) {
+        launch(std::true_type{});
+        return;
+      }
+    }
+    launch(std::false_type{});
   });
 }
 

@@ -33,6 +33,7 @@ struct FlashFwdArgs {
   int window;                 // sliding window, 0 = off
   const float* rel_bias;      // [H, Sq + Sk - 1], or null
   const int* doc_start;       // [B, Sq], or null
+  int q_off;  // forward only: query row i sits at key position q_off + i (0 = off)
 };
 
 struct FlashBwdArgs : FlashFwdArgs {

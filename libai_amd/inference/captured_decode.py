@@ -127,7 +127,8 @@ class _CapturedDecoderBase:
         assert L + max_new_tokens <= self.max_seq_len
         self.model.eval()
 
-        # 1) eager prefill (one big flash_fwd pass), fill the static caches
+        # 1) eager prefill (one big flash_fwd pass for a windowed model or one
+        # built with flash_prefill=True), fill the static caches
         out = self.model(input_ids=prompt_ids.to(self.device), use_cache=True)
         past = out["past_key_values"]
         logits = out["prediction_scores"]

@@ -14,6 +14,12 @@ Explicit re-design of the reference MultiheadAttention
     reference's fused_bias_add_dropout site (attention.py:265-267)
   * KV-cache incremental decoding (attention.py:201-208) and the
     cross-attention Q + KV split (attention.py:102-116).
+  * opt-in flash routes, both off by default: ``flash_prefill`` sends the
+    cached inference passes of a causal self-attention (prompt pass with
+    ``use_cache``, multi-token step on a past) through the flash forward with
+    the past length as the query offset; ``flash_cross_attention`` sends the
+    no-cache cross-attention call through the flash forward/backward on the
+    packed key/value projection.
 """
 
 import math
@@ -73,8 +79,16 @@ class MultiheadAttention(nn.Module):
         sequence_parallel=False,
         *,
         layer_idx=0,
+        flash_prefill=False,
+        flash_cross_attention=False,
     ):
         super().__init__()
+        # opt-in flash routes (both off: the layer is what it always was).
+        # flash_prefill: the cached inference passes of a causal self-attention
+        # (prompt pass with use_cache, multi-token step on a past).
+        # flash_cross_attention: the no-cache call of a cross-attention.
+        self.flash_prefill = flash_prefill
+        self.flash_cross_attention = flash_cross_attention
         self.hidden_size = hidden_size
         self.num_heads = num_attention_heads
         assert hidden_size % num_attention_heads == 0
@@ -180,7 +194,13 @@ class MultiheadAttention(nn.Module):
         # gradient (training / no-cache path only; the decode kernels take no
         # table).  Any other bias (Swin, user-supplied, a sliced T5 bias) has
         # neither attribute and takes the materialized path below.
-        from ..ops.attention import bias_alibi_slopes, bias_rel_table
+        from ..ops.attention import (
+            bias_alibi_slopes,
+            bias_rel_table,
+            flash_chunk_pays,
+            flash_prefill_available,
+            mask_kv_len,
+        )
 
         slopes = bias_alibi_slopes(position_bias)
         bias_fusable = position_bias is None or slopes is not None
@@ -230,6 +250,80 @@ class MultiheadAttention(nn.Module):
                     training=self.training,
                 )
 
+        if (
+            self.is_cross_attention
+            and self.flash_cross_attention
+            and past_key_value is None
+            and not use_cache
+            and position_bias is None
+        ):
+            from ..ops.attention import flash_attention_kv, flash_cross_available
+
+            b, sq, _ = hidden_states.shape
+            sk = encoder_states.shape[1]
+            if flash_cross_available(
+                self.head_size, hidden_states.dtype, hidden_states.device, sq, sk,
+                attention_mask,
+            ):
+                # both projections consumed as they come, zero copies: q as
+                # [b, sq, nh, hs], key_value as packed [b, sk, nh, 2, hs]
+                nh, hs = self.num_heads_local, self.head_size
+                q4 = self.query(hidden_states).view(b, sq, nh, hs)
+                kv5 = self.key_value(encoder_states).view(b, sk, nh, 2, hs)
+                o = flash_attention_kv(
+                    q4, kv5,
+                    scale=self.norm_factor * (self.coeff if self.coeff else 1.0),
+                    p_drop=self.attention_dropout_prob,
+                    training=self.training,
+                    kv_len=mask_kv_len(attention_mask),
+                )
+                out, bias = self.dense(o.reshape(b, sq, nh * hs))
+                if raw_output:
+                    return out, bias
+                return bias_dropout_add(
+                    out, bias=bias, residual=residual, p=self.output_dropout_prob,
+                    training=self.training,
+                )
+
+        # flash_prefill: the cached passes of a causal self-attention, in
+        # inference, with no mask but a right-padding one and no bias but ALiBi
+        prefill = False
+        if (
+            self.flash_prefill
+            and not self.is_cross_attention
+            and not self.training
+            and self.attn_mask_type == AttnMaskType.causal
+            and bias_fusable
+        ):
+            prefill = attention_mask is None or mask_kv_len(attention_mask) is not None
+        if prefill and use_cache and past_key_value is None:
+            from ..ops.attention import flash_attention_qkv
+
+            b, s, _ = hidden_states.shape
+            if flash_prefill_available(self.head_size, hidden_states.dtype,
+                                       hidden_states.device, s, s):
+                # prompt pass of any length (the key count may be ragged)
+                qkv = self.query_key_value(hidden_states)
+                qkv5 = qkv.view(b, s, self.num_heads_local, 3, self.head_size)
+                o = flash_attention_qkv(
+                    qkv5,
+                    scale=self.norm_factor * (self.coeff if self.coeff else 1.0),
+                    causal=True,
+                    training=False,
+                    kv_len=mask_kv_len(attention_mask),
+                    alibi_slopes=slopes,
+                )
+                # the cache layout, [b, nh, s, hs]: the views _split_heads gives
+                present = (qkv5[..., 1, :].permute(0, 2, 1, 3),
+                           qkv5[..., 2, :].permute(0, 2, 1, 3))
+                out, bias = self.dense(
+                    o.reshape(b, s, self.num_heads_local * self.head_size))
+                out = bias_dropout_add(
+                    out, bias=bias, residual=residual, p=self.output_dropout_prob,
+                    training=self.training,
+                )
+                return out, present
+
         if self.is_cross_attention:
             q = self._split_heads(self.query(hidden_states), 1)[0]
             if past_key_value is not None:
@@ -245,6 +339,31 @@ class MultiheadAttention(nn.Module):
         present = (k, v) if use_cache else None
 
         scale_d = self.norm_factor * (self.coeff if self.coeff else 1.0)
+        if (
+            prefill
+            and past_key_value is not None
+            and q.shape[2] > 1
+            and flash_prefill_available(self.head_size, q.dtype, q.device,
+                                        q.shape[2], k.shape[2])
+            and flash_chunk_pays(q.shape[0], q.shape[1], q.shape[2], k.shape[2])
+        ):
+            from ..ops.attention import flash_attention
+
+            # a chunk behind the cache: query i sits at key past_len + i; the
+            # kernel takes the head-major tensors through [b, s, nh, hs] views
+            o = flash_attention(
+                q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3),
+                scale_d, causal=True, training=False,
+                kv_len=mask_kv_len(attention_mask), alibi_slopes=slopes,
+                q_offset=past_key_value[0].shape[2],
+            )
+            b, sq, nh, hs = o.shape
+            out, bias = self.dense(o.reshape(b, sq, nh * hs))
+            out = bias_dropout_add(
+                out, bias=bias, residual=residual, p=self.output_dropout_prob,
+                training=self.training,
+            )
+            return (out, present) if use_cache else out
         if (
             past_key_value is not None
             and attention_mask is None

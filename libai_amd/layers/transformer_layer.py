@@ -43,6 +43,8 @@ class TransformerLayer(nn.Module):
         *,
         layer_idx=0,
         fuse_residual_norm=True,
+        flash_prefill=False,
+        flash_cross_attention=False,
     ):
         super().__init__()
         self.layer_idx = layer_idx
@@ -73,6 +75,7 @@ class TransformerLayer(nn.Module):
             attn_mask_type=attn_mask_type,
             sequence_parallel=sequence_parallel,
             layer_idx=layer_idx,
+            flash_prefill=flash_prefill,
         )
         self.post_attention_layernorm = LayerNorm(hidden_size, eps=layernorm_epsilon,
                                                   layer_idx=layer_idx)
@@ -85,6 +88,7 @@ class TransformerLayer(nn.Module):
                 output_layer_init_method=output_layer_init_method,
                 attn_mask_type=AttnMaskType.padding,
                 layer_idx=layer_idx,
+                flash_cross_attention=flash_cross_attention,
             )
             self.post_cross_attention_layernorm = LayerNorm(
                 hidden_size, eps=layernorm_epsilon, layer_idx=layer_idx

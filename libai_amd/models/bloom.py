@@ -39,6 +39,7 @@ class BloomModel(nn.Module):
         initializer_range=0.02,
         layernorm_eps=1e-5,
         apply_residual_post_layernorm=False,
+        flash_prefill=False,
     ):
         super().__init__()
         init_method = init_method_normal(initializer_range)
@@ -64,6 +65,7 @@ class BloomModel(nn.Module):
                 attn_mask_type=AttnMaskType.causal,
                 apply_residual_post_layernorm=apply_residual_post_layernorm,
                 layer_idx=i,
+                flash_prefill=flash_prefill,
             )
             for i in range(hidden_layers)
         ])
@@ -86,6 +88,7 @@ class BloomModel(nn.Module):
             "layernorm_eps": cfg.get("layernorm_eps", 1e-5),
             "apply_residual_post_layernorm": cfg.get(
                 "apply_residual_post_layernorm", False),
+            "flash_prefill": cfg.get("flash_prefill", False),
         }
 
     def alibi(self, seq_len, device, dtype):

@@ -65,7 +65,8 @@ class Transformer(nn.Module):
                  init_method, output_layer_init_method, bias_gelu_fusion,
                  bias_dropout_fusion, scale_mask_softmax_fusion,
                  apply_query_key_layer_scaling, apply_residual_post_layernorm,
-                 sequence_parallel=False, moe_num_experts=0, moe_top_k=2):
+                 sequence_parallel=False, moe_num_experts=0, moe_top_k=2,
+                 flash_prefill=False):
         super().__init__()
         self.num_layers = num_layers
         self.checkpoint_activations = False
@@ -89,6 +90,7 @@ class Transformer(nn.Module):
                     moe_num_experts=moe_num_experts or 8,
                     moe_top_k=moe_top_k,
                     layer_idx=i,
+                    flash_prefill=flash_prefill,
                 )
                 for i in range(num_layers)
             ]
@@ -145,6 +147,7 @@ class GPTModel(nn.Module):
         moe_num_experts=0,
         moe_top_k=2,
         amp_enabled=False,
+        flash_prefill=False,
     ):
         super().__init__()
         self.sequence_parallel = sequence_parallel
@@ -168,6 +171,7 @@ class GPTModel(nn.Module):
             apply_query_key_layer_scaling, apply_residual_post_layernorm,
             sequence_parallel=sequence_parallel,
             moe_num_experts=moe_num_experts, moe_top_k=moe_top_k,
+            flash_prefill=flash_prefill,
         )
         self.lm_head = LMLogits(vocab_size, bias=False,
                                 sequence_parallel=sequence_parallel, layer_idx=-1)
@@ -206,6 +210,7 @@ class GPTModel(nn.Module):
             "moe_num_experts": cfg.get("moe_num_experts", 0),
             "moe_top_k": cfg.get("moe_top_k", 2),
             "amp_enabled": cfg.get("amp_enabled", False),
+            "flash_prefill": cfg.get("flash_prefill", False),
         }
 
     def forward(self, input_ids, past_key_values=None, use_cache=False,

@@ -13,7 +13,12 @@ from torch.utils.checkpoint import checkpoint as act_checkpoint
 
 from ..config import configurable
 from ..layers import Linear1D, LMLogits, ParallelCrossEntropyLoss, RMSLayerNorm, VocabEmbedding
-from ..ops.attention import flash_attention, flash_attention_available
+from ..ops.attention import (
+    flash_attention,
+    flash_attention_available,
+    flash_chunk_pays,
+    flash_prefill_available,
+)
 from ..ops.rope import apply_rotary_pos_emb
 from ..ops.softmax import fused_scale_mask_softmax
 from ..ops.swiglu import swiglu
@@ -44,10 +49,13 @@ class LlamaAttention(nn.Module):
     def __init__(self, hidden_size, num_heads, max_position_embeddings,
                  init_method, output_init_method, rope_theta=10000.0,
                  num_key_value_heads=None, sequence_parallel=False,
-                 sliding_window=None, *, layer_idx=0):
+                 sliding_window=None, flash_prefill=False, *, layer_idx=0):
         super().__init__()
         assert sliding_window is None or sliding_window >= 0, sliding_window
         self.sliding_window = sliding_window or None  # None/0 = off
+        # opt-in: the cached inference passes (prompt pass with use_cache, a
+        # multi-token step on a past) go through the flash forward
+        self.flash_prefill = flash_prefill
         self.sequence_parallel = sequence_parallel
         self.hidden_size = hidden_size
         self.num_heads = num_heads
@@ -152,6 +160,22 @@ class LlamaAttention(nn.Module):
 
         window = self.sliding_window
         if (
+            self.flash_prefill
+            and use_cache
+            and past_key_value is None
+            and flash_prefill_available(self.head_dim, q.dtype, q.device, s, s)
+        ):
+            # prompt pass of any length (the key count may be ragged): no
+            # [b, nh, s, s] scores, no repeat_interleave of K and V; the cache
+            # gets every key, in [b, kvh, s, hd]
+            o = flash_attention(q, k, v, self.scale, p_drop=0.0, causal=True,
+                                training=False, window=window)
+            context = o.reshape(b, s, self.num_heads_local * self.head_dim)
+            present = (k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3))
+            out, _ = self.o_proj(context)
+            out = out + residual if residual is not None else out
+            return out, present
+        if (
             past_key_value is None
             # a windowed model also runs its prompt pass (use_cache) here, so
             # a long prefill never materializes S x S scores
@@ -192,6 +216,25 @@ class LlamaAttention(nn.Module):
                                         window=window)
                 context = ctx.permute(0, 2, 1, 3).reshape(
                     b, 1, self.num_heads_local * self.head_dim)
+                out, _ = self.o_proj(context)
+                out = out + residual if residual is not None else out
+                return (out, present) if use_cache else out
+            if (
+                self.flash_prefill
+                and past_key_value is not None
+                and s > 1
+                and flash_prefill_available(self.head_dim, q.dtype, q.device, s,
+                                            kh.shape[2])
+                and flash_chunk_pays(b, self.num_heads_local, s, kh.shape[2])
+            ):
+                # a chunk behind the cache: query i sits at key pos0 + i.  The
+                # kernel takes the head-major cache through [b, sk, kvh, hd]
+                # views and maps query heads to kv heads itself
+                o = flash_attention(q, kh.permute(0, 2, 1, 3),
+                                    vh.permute(0, 2, 1, 3), self.scale,
+                                    p_drop=0.0, causal=True, training=False,
+                                    window=window, q_offset=pos0)
+                context = o.reshape(b, s, self.num_heads_local * self.head_dim)
                 out, _ = self.o_proj(context)
                 out = out + residual if residual is not None else out
                 return (out, present) if use_cache else out
@@ -266,7 +309,7 @@ class LlamaDecoderLayer(nn.Module):
                  max_position_embeddings, rms_norm_eps, init_method,
                  output_init_method, rope_theta=10000.0,
                  num_key_value_heads=None, sequence_parallel=False,
-                 sliding_window=None, *, layer_idx=0):
+                 sliding_window=None, flash_prefill=False, *, layer_idx=0):
         super().__init__()
         self.layer_idx = layer_idx
         self.input_layernorm = RMSLayerNorm(hidden_size, eps=rms_norm_eps,
@@ -277,6 +320,7 @@ class LlamaDecoderLayer(nn.Module):
                                         num_key_value_heads,
                                         sequence_parallel=sequence_parallel,
                                         sliding_window=sliding_window,
+                                        flash_prefill=flash_prefill,
                                         layer_idx=layer_idx)
         self.post_attention_layernorm = RMSLayerNorm(hidden_size, eps=rms_norm_eps,
                                                      layer_idx=layer_idx)
@@ -350,6 +394,7 @@ class LlamaModel(nn.Module):
         sequence_parallel=False,
         amp_enabled=False,
         sliding_window=None,
+        flash_prefill=False,
     ):
         super().__init__()
         self.sequence_parallel = sequence_parallel
@@ -370,6 +415,7 @@ class LlamaModel(nn.Module):
                     output_init_method, rope_theta, num_key_value_heads,
                     sequence_parallel=sequence_parallel,
                     sliding_window=sliding_window,
+                    flash_prefill=flash_prefill,
                     layer_idx=i,
                 )
                 for i in range(hidden_layers)
@@ -402,6 +448,7 @@ class LlamaModel(nn.Module):
             "sequence_parallel": cfg.get("sequence_parallel", False),
             "amp_enabled": cfg.get("amp_enabled", False),
             "sliding_window": cfg.get("sliding_window", None),
+            "flash_prefill": cfg.get("flash_prefill", False),
         }
 
     def _run_layer(self, layer, h, past=None, use_cache=False, doc_start=None,

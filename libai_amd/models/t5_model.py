@@ -27,11 +27,22 @@ __all__ = ["T5Model", "T5ForPreTraining", "T5Loss"]
 
 
 def cross_attn_mask(dec_mask, enc_mask):
-    """[b, sq] x [b, sk] visibilities -> [b, sq, sk] uint8 (1=masked)."""
+    """[b, sq] x [b, sk] visibilities -> [b, sq, sk] uint8 (1=masked).
+
+    When the encoder visibility is pure right-padding (a contiguous prefix of
+    1s, the rule of ``extended_attn_mask``) the per-sequence valid key count
+    is attached as ``mask._kv_len``: the flash cross-attention consumes that
+    instead of the mask.  Padded *query* rows then attend the valid keys
+    instead of nothing, the contract BERT's padded rows already have; valid
+    rows are unaffected."""
     if dec_mask is None or enc_mask is None:
         return None
-    vis = dec_mask.to(torch.uint8).unsqueeze(2) * enc_mask.to(torch.uint8).unsqueeze(1)
-    return (1 - vis).to(torch.uint8)
+    em = enc_mask.to(torch.uint8)
+    vis = dec_mask.to(torch.uint8).unsqueeze(2) * em.unsqueeze(1)
+    mask = (1 - vis).to(torch.uint8)
+    if em.dim() == 2 and (em[:, :-1] >= em[:, 1:]).all():
+        mask._kv_len = em.sum(dim=-1, dtype=torch.int32)
+    return mask
 
 
 class T5Embedding(nn.Module):
@@ -89,6 +100,7 @@ class T5Model(nn.Module):
         relative_attention=False,
         relative_attention_num_buckets=32,
         relative_attention_max_distance=128,
+        flash_cross_attention=False,
     ):
         super().__init__()
         init_method = init_method_normal(initializer_range)
@@ -139,6 +151,7 @@ class T5Model(nn.Module):
                 mlp_type=mlp_type,
                 activation=activation,
                 layer_idx=i,
+                flash_cross_attention=flash_cross_attention and is_decoder,
             )
 
         # layer_idx spans encoder (0..n-1) then decoder (n..2n-1) for PP
@@ -182,6 +195,7 @@ class T5Model(nn.Module):
                 "relative_attention_num_buckets", 32),
             "relative_attention_max_distance": cfg.get(
                 "relative_attention_max_distance", 128),
+            "flash_cross_attention": cfg.get("flash_cross_attention", False),
         }
 
     def _run(self, layer, *args, **kw):

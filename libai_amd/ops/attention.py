@@ -37,6 +37,18 @@ walk only the tiles on the block diagonal.  Composes with GQA, dropout and
 ``kv_len``; not combinable with ``alibi_slopes``, ``window``, ``rel_bias`` or
 ``causal=False``, and needs Sq == Sk.
 
+Query offset (a chunk behind cached keys): ``flash_attention(...,
+q_offset=n)`` places query row i at key position n + i, so the causal mask,
+the window and the ALiBi distance are taken there; ``q_offset = Sk - Sq`` is
+the bottom-right alignment a ``cat([past, new])`` cache needs.  Inference
+only (no backward, no dropout); plain, ALiBi and window variants; the key
+count may be ragged.  ``q_offset = 0`` is the call it always was, top-left
+alignment for Sq != Sk included.
+
+Cross-attention (T5/MT5 decoder): ``flash_attention_kv`` takes the query
+projection and the packed [B, Sk, H, 2, D] key/value projection, non-causal,
+Sq != Sk; its backward writes dK and dV into one packed allocation.
+
 Replaces the reference's K2-K5 chain (reference
 libai/layers/attention.py:211-253).
 """
@@ -47,8 +59,10 @@ import torch
 
 from ._ext import draw_seed, ext
 
-__all__ = ["flash_attention", "flash_attention_qkv", "flash_attention_available",
-           "mask_kv_len", "bias_alibi_slopes", "bias_rel_table"]
+__all__ = ["flash_attention", "flash_attention_qkv", "flash_attention_kv",
+           "flash_attention_available", "flash_prefill_available",
+           "flash_cross_available", "flash_chunk_pays", "mask_kv_len", "bias_alibi_slopes",
+           "bias_rel_table"]
 
 
 def mask_kv_len(pad_mask):
@@ -156,6 +170,50 @@ def flash_attention_available(head_dim, dtype, device, sq, sk, pad_mask):
     )
 
 
+def flash_prefill_available(head_dim, dtype, device, sq, sk):
+    """The inference forward over cached keys (``flash_attention`` with
+    ``q_offset = sk - sq``, or the square prompt pass): any key count, ragged
+    included; no gradients."""
+    return (
+        device.type == "cuda"
+        and dtype == torch.bfloat16
+        and head_dim in (64, 128)
+        and 1 <= sq <= sk
+        and not torch.is_grad_enabled()
+    )
+
+
+# The chunk route runs one workgroup per 128 queries and head, and each walks
+# all the keys serially.  profiles/flash_prefill_cross.md, section 2, batch 1
+# and 32 heads: with 32 workgroups (chunks up to 128 tokens) it measured
+# faster than the materialized route on 256 to 1024 cached keys, 1.1-1.5x
+# slower on 2048 and 1.5-2.2x slower on 4096; with 128 workgroups (a 512-token
+# chunk) 1.04-1.23x slower on 4096.  Long caches under few workgroups keep the
+# materialized route; fuller grids were not measured.
+FLASH_CHUNK_LONG_CACHE = 2048      # keys
+FLASH_CHUNK_FEW_WORKGROUPS = 128   # batch * heads * ceil(sq / 128)
+
+
+def flash_chunk_pays(batch, heads, sq, sk):
+    """Whether a chunk of sq queries behind a cache (sk keys in all) should
+    take the flash forward: not a few workgroups walking a long cache."""
+    workgroups = batch * heads * -(-sq // 128)
+    return sk < FLASH_CHUNK_LONG_CACHE or workgroups > FLASH_CHUNK_FEW_WORKGROUPS
+
+
+def flash_cross_available(head_dim, dtype, device, sq, sk, pad_mask):
+    """Non-causal attention of sq queries over sk other keys
+    (``flash_attention_kv``), forward and backward."""
+    return (
+        device.type == "cuda"
+        and dtype == torch.bfloat16
+        and head_dim in (64, 128)
+        and (pad_mask is None or mask_kv_len(pad_mask) is not None)
+        and sk % 8 == 0
+        and sq >= 1
+    )
+
+
 class _FlashAttnQKVFn(torch.autograd.Function):
     """Packed-qkv variant: takes the fused [B, S, H, 3, D] projection buffer
     directly.  The backward writes dQ/dK/dV straight into one packed dqkv
@@ -233,9 +291,65 @@ class _FlashAttnFn(torch.autograd.Function):
         return (dq, dk, dv, None, None, None, None) + _variant_grads(ctx, 7, grads)
 
 
+class _FlashAttnKVFn(torch.autograd.Function):
+    """Cross-attention on the packed key/value projection: q [B, Sq, H, D] and
+    kv5 [B, Sk, H, 2, D], non-causal.  The backward writes dK/dV straight into
+    one packed dkv allocation, as _FlashAttnQKVFn does with dqkv."""
+
+    @staticmethod
+    def forward(ctx, q, kv5, scale, p_drop, kv_len):
+        seed = draw_seed() if p_drop > 0 else 0
+        o, lse = ext().flash_fwd(q, kv5[..., 0, :], kv5[..., 1, :], scale, p_drop,
+                                 seed, False, kv_len)
+        ctx.save_for_backward(q, kv5, o, lse)
+        ctx.kv_len = kv_len
+        ctx.meta = (scale, p_drop, seed)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, kv5, o, lse = ctx.saved_tensors
+        scale, p_drop, seed = ctx.meta
+        dkv = torch.empty_like(kv5)
+        dq = ext().flash_bwd(
+            q, kv5[..., 0, :], kv5[..., 1, :], o, do.contiguous(), lse, scale,
+            p_drop, seed, False, None, ctx.kv_len, dkv=dkv,
+        )[0]
+        return dq, dkv, None, None, None
+
+
+def flash_attention_kv(q, kv5, scale, p_drop=0.0, training=True, kv_len=None):
+    """q: [B, Sq, H, D], kv5: packed [B, Sk, H, 2, D] bf16 -> O [B, Sq, H, D]
+    (zero-copy in/out).  Non-causal: every query sees every key below
+    kv_len[b] (optional int32 [B]).  Sq and Sk are independent."""
+    if kv5.dim() != 5 or kv5.shape[3] != 2:
+        raise ValueError(f"kv5 must be [B, Sk, H, 2, D], got {tuple(kv5.shape)}")
+    return _FlashAttnKVFn.apply(q, kv5, scale, p_drop if training else 0.0, kv_len)
+
+
+def _check_q_offset(q_offset, sq, sk, causal, p_drop, rel_bias, doc_bounds):
+    """The rules of a non-zero query offset, before anything reaches the
+    extension."""
+    if q_offset < 0:
+        raise ValueError(f"q_offset must be >= 0, got {q_offset}")
+    if q_offset == 0:
+        return
+    if not causal:
+        raise ValueError("q_offset requires causal attention")
+    if p_drop > 0:
+        raise ValueError("q_offset cannot be combined with dropout")
+    if rel_bias is not None:
+        raise ValueError("q_offset cannot be combined with rel_bias")
+    if doc_bounds is not None:
+        raise ValueError("q_offset cannot be combined with doc_bounds")
+    if q_offset + sq > sk:
+        raise ValueError(f"q_offset + Sq must not exceed Sk "
+                         f"({q_offset} + {sq} > {sk})")
+
+
 def flash_attention(q, k, v, scale, p_drop=0.0, causal=True, training=True,
                     kv_len=None, alibi_slopes=None, window=None, rel_bias=None,
-                    doc_bounds=None):
+                    doc_bounds=None, q_offset=0):
     """q, k, v: [B, S, H, D] bf16 -> O [B, S, H, D].
 
     alibi_slopes: optional fp32 [H] (query heads) — fused ALiBi bias.
@@ -247,11 +361,24 @@ def flash_attention(q, k, v, scale, p_drop=0.0, causal=True, training=True,
     doc_bounds: optional (doc_start, doc_end), int32 [B, S] each — packed
     documents: causal attention that stays inside the query's own document
     (needs Sq == Sk; not combinable with alibi_slopes, window, rel_bias or
-    causal=False)."""
+    causal=False).
+    q_offset: optional int n > 0 — query row i sits at key position n + i (a
+    chunk behind n cached keys; n = Sk - Sq for a cat([past, new]) cache).
+    Inference only: causal, no dropout, no gradients, plain / alibi_slopes /
+    window; Sk may be ragged.  0 = off."""
+    q_offset = int(q_offset)
+    p_drop = p_drop if training else 0.0
+    _check_q_offset(q_offset, q.shape[1], k.shape[1], causal, p_drop, rel_bias,
+                    doc_bounds)
     variant = _variant_args(k.shape[1], causal, alibi_slopes, window, rel_bias,
                             doc_bounds)
-    return _FlashAttnFn.apply(q, k, v, scale, p_drop if training else 0.0, causal,
-                              kv_len, *variant)
+    if q_offset > 0:
+        if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad
+                                        or v.requires_grad):
+            raise ValueError("q_offset is an inference path: it has no backward")
+        return ext().flash_fwd(q, k, v, scale, 0.0, 0, True, kv_len, *variant,
+                               q_offset)[0]
+    return _FlashAttnFn.apply(q, k, v, scale, p_drop, causal, kv_len, *variant)
 
 
 def decode_attention_available(q, head_dim):
