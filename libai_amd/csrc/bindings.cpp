@@ -711,6 +711,51 @@ std::tuple<torch::Tensor, torch::Tensor> flash_fwd(torch::Tensor q, torch::Tenso
   return {o, lse};
 }
 
+// Split-KV forward (inference): the keys are cut into splits of split_keys
+// keys that run as separate workgroups; a merge kernel folds their partial
+// states.  Plain, ALiBi and window; q_offset 0 allowed, causal or not.
+std::tuple<torch::Tensor, torch::Tensor> flash_fwd_split(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, double scale, bool causal,
+    c10::optional<torch::Tensor> kv_len, c10::optional<torch::Tensor> alibi_slopes,
+    int64_t window, int64_t q_offset, int64_t split_keys) {
+  const int* kvl = kv_len_ptr(kv_len, q.size(0), /*contiguous=*/true);
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4);
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "flash_fwd_split is bf16-only");
+  TORCH_CHECK(q.stride(3) == 1 && k.stride(3) == 1 && v.stride(3) == 1);
+  const int B = (int)q.size(0), Sq = (int)q.size(1), H = (int)q.size(2),
+            D = (int)q.size(3);
+  const int Sk = (int)k.size(1), Hkv = (int)k.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
+  TORCH_CHECK(Hkv > 0 && H % Hkv == 0 && (int)v.size(2) == Hkv,
+              "GQA head counts: H divisible by Hkv, v matches k");
+  TORCH_CHECK(Sq >= 1 && Sk >= 1, "flash_fwd_split: empty q or k");
+  TORCH_CHECK(split_keys > 0 && split_keys % 128 == 0,
+              "flash_fwd_split: split_keys must be a positive multiple of 128");
+  const VariantPtrs var =
+      variant_ptrs("flash_fwd_split", q, B, H, Sq, Sk, causal, alibi_slopes, window,
+                   c10::nullopt, c10::nullopt, c10::nullopt, q_offset);
+  const int64_t NS = (Sk + split_keys - 1) / split_keys;
+  const auto f32 = q.options().dtype(torch::kFloat32);
+  auto o = torch::empty({B, Sq, H, D}, q.options());
+  auto lse = torch::empty({B, H, Sq}, f32);
+  // uninitialized: the kernels write every state, and the merge reads the
+  // part_acc of live states only
+  auto part_m = torch::empty({B, H, Sq, NS}, f32);
+  auto part_l = torch::empty({B, H, Sq, NS}, f32);
+  auto part_acc = torch::empty({B, H, Sq, NS, D}, f32);
+  FlashSplitArgs a{};
+  static_cast<FlashFwdArgs&>(a) =
+      flash_args(q, k, v, o, lse, kvl, scale, 0.0, 0, causal, var);
+  a.q_off = (int)q_offset;
+  a.part_m = part_m.data_ptr<float>();
+  a.part_l = part_l.data_ptr<float>();
+  a.part_acc = part_acc.data_ptr<float>();
+  a.split_keys = (int)split_keys;
+  flash_fwd_split_bf16(a, cur_stream());
+  check_launch("flash_fwd_split");
+  return {o, lse};
+}
+
 // Returns (dq, dk, dv), or (dq, dk, dv, d_rel_bias) when a relative-position
 // table is given (fp32, the table's shape, summed over the batch).
 py::tuple flash_bwd(
@@ -966,6 +1011,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kv_len"), py::arg("alibi_slopes") = py::none(), py::arg("window") = 0,
         py::arg("rel_bias") = py::none(), py::arg("doc_start") = py::none(),
         py::arg("doc_end") = py::none(), py::arg("q_offset") = 0);
+  m.def("flash_fwd_split", &flash_fwd_split, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("scale"), py::arg("causal"), py::arg("kv_len"),
+        py::arg("alibi_slopes"), py::arg("window"), py::arg("q_offset"),
+        py::arg("split_keys"));
+  m.def("flash_split_keys_auto", &flash_split_keys_auto, py::arg("B"), py::arg("Hkv"),
+        py::arg("kv_group"), py::arg("Sq"), py::arg("Sk"));
   m.def("flash_bwd", &flash_bwd, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o"), py::arg("dout"), py::arg("lse"), py::arg("scale"),
         py::arg("p_drop"), py::arg("seed"), py::arg("causal"), py::arg("dqkv"),

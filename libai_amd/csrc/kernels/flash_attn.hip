@@ -598,6 +598,345 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
 }
 
 // ===========================================================================
+// split-KV forward: a short query chunk behind a long cache (inference)
+// ===========================================================================
+// The forward above gives one workgroup 128 queries of ONE head and lets it
+// walk every key: a chunk of up to 128 tokens on 32 heads is 32 workgroups on
+// 256 CUs, each with Sk / 128 serial staging rounds, and with Sq = 8 three
+// quarters of every wave's MFMA columns are padding.  This kernel changes how
+// the work is split, not how a tile is computed:
+//   * grid (ceil(G * Sq / 128), B * Hkv, NS): split s owns keys
+//     [s * split_keys, min((s + 1) * split_keys, kv_end)) and runs the
+//     forward's 2-barrier round loop on those rounds only (split_keys is a
+//     multiple of the 128 keys of a round, so no sub-tile straddles a split);
+//   * packed rows: a workgroup serves one KV head and 128 rows r of
+//     [0, G * Sq), head-major: row r is query head hk * G + r / Sq at row
+//     r % Sq.  In the swapped S = K x Q^T layout a lane owns one query column,
+//     so packing costs per-lane values computed once in the prologue (q
+//     pointer, position pg, ALiBi slope) and K / V are staged once per KV head
+//     for all G query heads.  Lanes past G * Sq load a clamped row and store
+//     nothing;
+//   * wave-uniform bounds: a wave's (and the tile's) rows [r0, r1] span the
+//     positions [q_off + r0 % Sq, q_off + r1 % Sq] inside one head and
+//     [q_off, q_off + Sq - 1] across a head boundary (exact: such a run holds
+//     a last and a first row).  These take the place of the forward's p_base /
+//     p_base + 31 / p_block in every skip and in the tile class; the
+//     per-element predicate keeps the lane's own pg;
+//   * a split with nothing visible for the whole tile leaves before its first
+//     barrier and writes the null state m = -3.0e38, l = 0; a row that sees no
+//     key of a live split ends in the same state through the edge body.
+// Output: fp32 partial states, part_m / part_l [B, H, Sq, NS] (m in the exp2
+// domain, ALiBi included; l unnormalized) and part_acc [B, H, Sq, NS, D]
+// (unnormalized O).  A lane's register runs are 4 consecutive d, so every
+// part_acc store is 16 bytes.  flash_split_merge_kernel folds the splits.
+// No dropout, no rel_bias, no documents; q_off is a plain argument (0 allowed).
+//
+// Packed fp32 VALU forms (v_pk_mul / add / fma_f32) are switched off for these
+// two kernels by a function attribute; the alpha rescale of the accumulators
+// and the merge's 4-wide fma are what the compiler would otherwise pack.  A
+// function with other target features is not inlined into them: the kernel's
+// lambdas therefore carry the attribute too, and the three HIP header helpers
+// the forward uses (__syncthreads, __shfl_xor, make_float4) are replaced by
+// the builtin forms below, so the round loop holds two s_barrier and no call.
+#define SPLIT_TARGET __attribute__((target("no-packed-fp32-ops")))
+
+// __syncthreads(): workgroup release fence, s_barrier, acquire fence
+__device__ __forceinline__ SPLIT_TARGET void split_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// x of lane l and of lane l ^ 32, as {value of the lower-half lane, value of
+// the upper-half lane} on both: v_permlane32_swap of x with itself.  max and
+// + of the pair are what x op __shfl_xor(x, 32) gives, bit for bit.
+__device__ __forceinline__ SPLIT_TARGET void half_pair(float x, float& lo, float& up) {
+  const uint32_t u = __builtin_bit_cast(uint32_t, x);
+  auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  lo = __builtin_bit_cast(float, (uint32_t)r[0]);
+  up = __builtin_bit_cast(float, (uint32_t)r[1]);
+}
+
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+
+template <int D, FlashVariant V>
+__global__ __launch_bounds__(256, D == 64 ? 3 : 2) SPLIT_TARGET
+    void flash_fwd_split_kernel(
+        const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+        const bf16_t* __restrict__ v, float* __restrict__ part_m,
+        float* __restrict__ part_l, float* __restrict__ part_acc,
+        const int* __restrict__ kv_len, int64_t q_sb, int64_t q_ss, int64_t q_sh,
+        int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sb, int64_t v_ss,
+        int64_t v_sh, int H, int Sq, int Sk, float scale, int causal, int kv_group,
+        const float* __restrict__ alibi_slopes, int window, int q_off,
+        int split_keys) {
+  constexpr bool ALIBI = V == FlashVariant::kAlibi,
+                 WINDOW = V == FlashVariant::kWindow;
+  static_assert(V == FlashVariant::kPlain || ALIBI || WINDOW,
+                "split-KV: plain, ALiBi and window only");
+  constexpr int DT = D / 32;
+  constexpr int KC = D / 16;
+
+  __shared__ __align__(16) bf16_t k_lds[2 * KVB * D];
+  __shared__ __align__(16) bf16_t v_lds[2 * KVB * D];
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int l31 = lane & 31;
+  const int hi = lane >> 5;
+
+  const int Hkv = H / kv_group;
+  const int b = blockIdx.y / Hkv, hk = blockIdx.y % Hkv;
+  const int split = blockIdx.z, NS = gridDim.z;
+  const int GS = kv_group * Sq;  // packed rows of this KV head
+  const int r_block = blockIdx.x * QBLK;
+  const int r_base = __builtin_amdgcn_readfirstlane(r_block + wave * QB);
+
+  // lane's packed row -> its query head, its row there, its key position
+  const int rl = r_base + l31;
+  const int rc = min(rl, GS - 1);
+  const int h = hk * kv_group + rc / Sq;
+  const int qi = rc % Sq;
+  const int pg = q_off + qi;
+  const int64_t prow = ((int64_t)(b * H + h) * Sq + qi) * NS + split;
+
+  // positions of the rows [r0, r1] (r0 <= r1 < GS, wave-uniform), see above
+  auto pos_range = [&](int r0, int r1, int& lo, int& up) SPLIT_TARGET {
+    const int g0 = r0 / Sq, g1 = r1 / Sq;
+    const bool one_head = g0 == g1;
+    lo = __builtin_amdgcn_readfirstlane(one_head ? q_off + (r0 - g0 * Sq) : q_off);
+    up = __builtin_amdgcn_readfirstlane(one_head ? q_off + (r1 - g1 * Sq)
+                                                 : q_off + Sq - 1);
+  };
+  int p_lo, p_hi, tp_lo, tp_hi;  // this wave's range and the tile's
+  pos_range(min(r_base, GS - 1), min(r_base + QB - 1, GS - 1), p_lo, p_hi);
+  pos_range(r_block, min(r_block + QBLK - 1, GS - 1), tp_lo, tp_hi);
+
+  const int sk_eff = (kv_len != nullptr) ? kv_len[b] : Sk;
+  const int kv_end = causal ? min(sk_eff, tp_hi + 1) : sk_eff;
+  const int split_lo = split * split_keys;
+  const int split_hi = min(split_lo + split_keys, kv_end);
+
+  // Null split: nothing visible for the whole tile (workgroup-uniform, before
+  // the first barrier).  split_lo >= kv_end is split_lo >= sk_eff or, under
+  // causal, split_lo > the tile's highest position.
+  bool null_split = split_lo >= kv_end;
+  if constexpr (WINDOW) null_split = null_split || split_hi - 1 < tp_lo - window + 1;
+  if (null_split) {
+    if (rl < GS && hi == 0) {
+      part_m[prow] = -3.0e38f;
+      part_l[prow] = 0.f;
+    }
+    return;
+  }
+
+  const bf16_t* kp = k + b * k_sb + hk * k_sh;
+  const bf16_t* vp = v + b * v_sb + hk * v_sh;
+
+  // Q fragments pre-scaled by scale*log2e, as in the forward
+  const float qscale = scale * 1.4426950408889634f;
+  bf16x8_t qfrag[KC];
+  {
+    const bf16_t* qp = q + b * q_sb + h * q_sh + (int64_t)qi * q_ss;
+#pragma unroll
+    for (int c = 0; c < KC; ++c) {
+      bf16x8_t raw = *(const bf16x8_t*)(qp + c * 16 + hi * 8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) raw[j] = (bf16_t)((float)raw[j] * qscale);
+      qfrag[c] = raw;
+    }
+  }
+
+  f32x16_t oacc[DT];
+#pragma unroll
+  for (int t = 0; t < DT; ++t) oacc[t] = f32x16_t{};
+  float m_run = -3.0e38f, l_run = 0.f;
+
+  // the lane's OWN head's slope (a wave can hold several heads)
+  float slope2 = 0.f;
+  if constexpr (ALIBI) slope2 = alibi_slopes[h] * 1.4426950408889634f;
+
+  int round0 = split_lo / (2 * KVB);
+  if constexpr (WINDOW)
+    round0 = max(round0, max(0, tp_lo - window + 1) / (2 * KVB));
+  const int n_rounds = CDIV(split_hi, 2 * KVB);
+
+  for (int round = round0; round < n_rounds; ++round) {
+    const int kvR = round * 2 * KVB;
+    split_barrier();
+    stage_tile<2 * KVB, D, true, false>(k_lds, nullptr, kp, kvR, Sk, k_ss, tid);
+    stage_tile<2 * KVB, D, false, true>(nullptr, v_lds, vp, kvR, Sk, v_ss, tid);
+    split_barrier();
+
+    // rolled: unrolled, the plain and ALiBi bodies at D=64 need ~180 VGPRs
+    // and spill at the 3-wave budget of 168
+#pragma unroll 1
+    for (int sub = 0; sub < 2; ++sub) {
+    const int kv0 = kvR + sub * KVB;
+    const int ro = sub * KVB;  // row offset inside the staged images
+    if (kv0 >= split_hi || (causal && kv0 > p_hi)) continue;
+    if constexpr (WINDOW) {  // sub-tile entirely below this wave's band
+      if (kv0 + KVB - 1 < p_lo - window + 1) continue;
+    }
+
+    // S = K x Q^T : two 32x32 tiles
+    f32x16_t s0{}, s1{};
+#pragma unroll
+    for (int c = 0; c < KC; ++c) {
+      bf16x8_t ka = row_img_frag<D>(k_lds, ro + l31, c, hi);
+      s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qfrag[c], s0, 0, 0, 0);
+      bf16x8_t kb = row_img_frag<D>(k_lds, ro + l31 + 32, c, hi);
+      s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kb, qfrag[c], s1, 0, 0, 0);
+    }
+
+    float sv[2][16];
+    // tile class, as in the forward, on the wave's position range
+    bool interior = kv0 + KVB <= sk_eff && r_base + QB <= GS &&
+                    (!causal || p_lo >= kv0 + KVB - 1);
+    if constexpr (WINDOW) interior = interior && (p_hi - kv0 < window);
+    auto softmax_tile = [&](auto masked_c) SPLIT_TARGET {
+      constexpr bool MASKED = decltype(masked_c)::value;
+      float pmax = -3.0e38f;
+      float rel0 = 0.f;
+      if constexpr (ALIBI) rel0 = (float)(kv0 + 4 * hi - pg);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        int kva = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        int kvb = kva + 32;
+        float a = s0[r], bb = s1[r];
+        if constexpr (ALIBI) {  // before the masks: masked entries keep the sentinel
+          const float off = (float)((r & 3) + 8 * (r >> 2));
+          a = fmaf(slope2, rel0 + off, a);
+          bb = fmaf(slope2, rel0 + (off + 32.f), bb);
+        }
+        if constexpr (MASKED) {
+          if (kva >= sk_eff || (causal && kva > pg)) a = -3.0e38f;
+          if (kvb >= sk_eff || (causal && kvb > pg)) bb = -3.0e38f;
+          if constexpr (WINDOW) {
+            if (pg - kva >= window) a = -3.0e38f;
+            if (pg - kvb >= window) bb = -3.0e38f;
+          }
+        }
+        sv[0][r] = a;
+        sv[1][r] = bb;
+        pmax = fmaxf(pmax, fmaxf(a, bb));
+      }
+      float half_lo, half_up;  // the two halves of this query column
+      half_pair(pmax, half_lo, half_up);
+      pmax = fmaxf(half_lo, half_up);
+
+      const float m_new = fmaxf(m_run, pmax);
+      float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+      if constexpr (MASKED) alpha = (m_run <= -3.0e38f) ? 0.f : alpha;
+      m_run = m_new;
+      float lsum = 0.f;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float e = __builtin_amdgcn_exp2f(sv[t][r] - m_new);
+          if constexpr (MASKED) e = (sv[t][r] <= -3.0e38f) ? 0.f : e;
+          sv[t][r] = e;
+          lsum += e;
+        }
+      half_pair(lsum, half_lo, half_up);
+      lsum = half_lo + half_up;
+      l_run = l_run * alpha + lsum;
+      return alpha;
+    };
+    const float alpha = interior ? softmax_tile(std::false_type{})
+                                 : softmax_tile(std::true_type{});
+#pragma unroll
+    for (int t = 0; t < DT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) oacc[t][r] *= alpha;
+
+    // PV: O^T[d][q] += V^T x P
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+      for (int c16 = 0; c16 < 2; ++c16) {
+        bf16x8_t pfrag = repack_chunk(&sv[t][c16 * 8]);
+        const int kvc = t * 32 + c16 * 16;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) {
+          bf16x8_t vfrag = tr_img_frag<D>(v_lds, ro + kvc, dt, lane);
+          oacc[dt] =
+              __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfrag, pfrag, oacc[dt], 0, 0, 0);
+        }
+      }
+    }
+    }  // sub
+  }
+
+  if (rl < GS) {
+    float* ap = part_acc + prow * D;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4)
+        *(f32x4_t*)(ap + dt * 32 + 8 * r4 + 4 * hi) =
+            f32x4_t{oacc[dt][r4 * 4], oacc[dt][r4 * 4 + 1], oacc[dt][r4 * 4 + 2],
+                    oacc[dt][r4 * 4 + 3]};
+    if (hi == 0) {
+      part_m[prow] = m_run;
+      part_l[prow] = l_run;
+    }
+  }
+}
+
+// Folds the NS partial states of every row (b, h, i), in split order (no
+// atomics: the same bits on every run):
+//   M = max m_s;  a_s = exp2(m_s - M);  L = sum a_s l_s;
+//   o = bf16(sum a_s acc_s / L), exact zeros when L == 0;
+//   lse = M * ln2 + log(L).
+// A null state (m = -3.0e38) contributes nothing and its part_acc is NOT read:
+// the workspace is uninitialized there and 0 * garbage may be NaN.
+// Mapping: D / 4 lanes per row, four consecutive d each (16-byte part_acc loads,
+// 8-byte o stores), so a wave folds 4 rows at D = 64 and 2 at D = 128; each
+// lane walks the splits of its row itself, the m / l loads being broadcasts.
+template <int D>
+__global__ __launch_bounds__(256) SPLIT_TARGET void flash_split_merge_kernel(
+    const float* __restrict__ part_m, const float* __restrict__ part_l,
+    const float* __restrict__ part_acc, bf16_t* __restrict__ o,
+    float* __restrict__ lse, int64_t o_sb, int64_t o_ss, int64_t o_sh, int H, int Sq,
+    int NS, int64_t nrows) {
+  constexpr int LPR = D / 4;      // lanes per row
+  constexpr int RPB = 256 / LPR;  // rows per workgroup
+  const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;  // (b*H+h)*Sq+i
+  if (row >= nrows) return;
+  const int c4 = (threadIdx.x % LPR) * 4;
+  const float* pm = part_m + row * NS;
+  const float* pl = part_l + row * NS;
+  const float* pa = part_acc + row * NS * D + c4;
+
+  float M = -3.0e38f;
+  for (int s = 0; s < NS; ++s) M = fmaxf(M, pm[s]);
+  float L = 0.f;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < NS; ++s) {
+    const float m = pm[s];
+    if (m <= -3.0e38f) continue;
+    const float a = __builtin_amdgcn_exp2f(m - M);
+    L = fmaf(a, pl[s], L);
+    const f32x4_t x = *(const f32x4_t*)(pa + (int64_t)s * D);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = fmaf(a, x[j], acc[j]);
+  }
+  const float inv_l = (L > 0.f) ? 1.0f / L : 0.f;
+  const int64_t bh = row / Sq;
+  const int i = (int)(row % Sq);
+  const int64_t b = bh / H, h = bh % H;
+  bf16x4_t pk;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) pk[j] = (bf16_t)(acc[j] * inv_l);
+  *(bf16x4_t*)(o + b * o_sb + i * o_ss + h * o_sh + c4) = pk;
+  if (c4 == 0)
+    lse[row] = M * 0.6931471805599453f + __logf(L > 0.f ? L : 1.f);
+}
+
+// ===========================================================================
 // Drow = rowsum(dO * O): one wave per 8 rows (8 lanes x 8 elems for D=64)
 // out layout [B*H, Sq] (matches lse); inputs [B, Sq, H, D] strided
 // ===========================================================================
@@ -1419,6 +1758,73 @@ extern "C" void flash_fwd_bf16(const FlashFwdArgs& a, hipStream_t stream) {
       }
     }
     launch(std::false_type{});
+  });
+}
+
+// Keys per split for a chunk of Sq queries on Sk keys, or 0 for "do not
+// split".  A pure function of its arguments.
+// profiles/flash_split_chunk.md (LlamaAttention, hidden 4096, D 128, batch 1,
+// 32 and 8 KV heads, chunks of 2 to 512 tokens on 1024 to 4096 cached keys,
+// split_keys swept over 128..1024): the best split size grows with the tile
+// count and the key count, and the fastest measured setting of every row
+// has 256 to 512 workgroups (128 tiles x 4 splits of 1152 keys down to 8
+// tiles x 32 splits of 128 keys).  With that target the split route measured
+// below the single-pass kernel at every row and below the materialized route
+// at every row but one class: thin tiles, with less than one wave of real
+// rows (G * Sq < 32).  With 32 such tiles they win on 2048 cached keys (0.71
+// to 0.81 of the materialized route) and are at parity with it on 4096 (0.96
+// to 1.02), which is no gain; nothing in between was measured.  Thin tiles
+// therefore split only up to the largest staging volume, tiles x keys, that
+// was measured to win (32 tiles on 2048 + 16 keys; 8 thin tiles on 4096 keys
+// lie below it and win too).
+// Not measured, so no split: fewer than 1024 keys, more than 128 tiles, a
+// batch above 1.  The policy does not see the head size: D = 64 was not
+// measured and follows the D = 128 figures, an extrapolation.
+#define SPLIT_MIN_KEYS 1024    // keys
+#define SPLIT_THIN_ROWS QB     // packed rows per KV head: less than one wave
+#define SPLIT_THIN_STAGING (32 * 2064)  // tiles * keys
+#define SPLIT_MAX_TILES 128    // Hkv * ceil(G * Sq / 128) at batch 1
+#define SPLIT_TARGET_WGS 512   // workgroups, tiles * splits
+#define SPLIT_MIN_SPLIT 128    // keys per split, one staging round
+extern "C" int flash_split_keys_auto(int B, int Hkv, int kv_group, int Sq, int Sk) {
+  if (B <= 0 || Hkv <= 0 || kv_group <= 0 || Sq <= 0 || Sk <= 0) return 0;
+  const int64_t tiles = (int64_t)B * Hkv * CDIV((int64_t)kv_group * Sq, QBLK);
+  if (B > 1 || Sk < SPLIT_MIN_KEYS || tiles > SPLIT_MAX_TILES) return 0;
+  if (kv_group * Sq < SPLIT_THIN_ROWS && tiles * Sk > SPLIT_THIN_STAGING) return 0;
+  // the fewest splits that give SPLIT_TARGET_WGS workgroups, in whole rounds
+  const int64_t want = CDIV((int64_t)SPLIT_TARGET_WGS, tiles);
+  const int64_t keys = CDIV(CDIV((int64_t)Sk, want), 2 * KVB) * 2 * KVB;
+  return keys < SPLIT_MIN_SPLIT ? SPLIT_MIN_SPLIT : (int)keys;
+}
+
+extern "C" void flash_fwd_split_bf16(const FlashSplitArgs& a, hipStream_t stream) {
+  const int Hkv = a.H / a.kv_group;
+  const int NS = CDIV(a.Sk, a.split_keys);
+  const dim3 grid(CDIV(a.kv_group * a.Sq, QBLK), a.B * Hkv, NS), block(256);
+  const int window = clamp_window(a.window, a.Sq, a.Sk);
+  const FlashVariant variant =
+      flash_variant(a.alibi_slopes, window, a.rel_bias, a.doc_start);
+  const int64_t rows = (int64_t)a.B * a.H * a.Sq;
+  flash_dispatch(a.D, variant, [&](auto dc, auto vc) {
+    constexpr int DD = decltype(dc)::value;
+    constexpr FlashVariant VV = decltype(vc)::value;
+    // no split instantiation takes rel_bias or documents (the binding passes
+    // neither)
+    if constexpr (VV == FlashVariant::kPlain || VV == FlashVariant::kAlibi ||
+                  VV == FlashVariant::kWindow) {
+      flash_fwd_split_kernel<DD, VV><<<grid, block, 0, stream>>>(
+          in(a.q), in(a.k), in(a.v), a.part_m, a.part_l, a.part_acc, a.kv_len,
+          a.q.sb, a.q.ss, a.q.sh,
+          a.k.sb, a.k.ss, a.k.sh,
+          a.v.sb, a.v.ss, a.v.sh,
+          a.H, a.Sq, a.Sk, a.scale, a.causal, a.kv_group, a.alibi_slopes, window,
+          a.q_off, a.split_keys);
+      constexpr int RPB = 256 / (DD / 4);
+      flash_split_merge_kernel<DD>
+          <<<dim3((uint32_t)CDIV(rows, RPB)), block, 0, stream>>>(
+              a.part_m, a.part_l, a.part_acc, out(a.o), a.lse, a.o.sb, a.o.ss,
+              a.o.sh, a.H, a.Sq, NS, rows);
+    }
   });
 }
 

@@ -43,6 +43,17 @@ struct FlashBwdArgs : FlashFwdArgs {
   const int* doc_end;            // [B, Sq]; set together with doc_start
 };
 
+// Split-KV forward (inference; plain, ALiBi and window; no dropout): the key
+// range is cut into splits of split_keys keys that run as separate workgroups
+// and leave fp32 partial softmax states, which a merge kernel folds into o and
+// lse.  p_drop, rel_bias and doc_start must be 0 / null.
+struct FlashSplitArgs : FlashFwdArgs {
+  // NS = ceil(Sk / split_keys) states per row
+  float *part_m, *part_l;  // [B, H, Sq, NS]: running max (exp2 domain), sum
+  float* part_acc;         // [B, H, Sq, NS, D]: unnormalized O
+  int split_keys;          // a positive multiple of 128
+};
+
 // NAME_bf16 and NAME_f32 with one parameter list (the .hip files define the
 // pairs from one macro body too)
 #define BF16_F32(RET, NAME, ...) \
@@ -53,6 +64,10 @@ extern "C" {
 
 void flash_fwd_bf16(const FlashFwdArgs& args, hipStream_t stream);
 void flash_bwd_bf16(const FlashBwdArgs& args, hipStream_t stream);
+void flash_fwd_split_bf16(const FlashSplitArgs& args, hipStream_t stream);
+// keys per split for a chunk of Sq queries on Sk keys (a multiple of 128), or
+// 0 for "do not split"; a pure function of its arguments
+int flash_split_keys_auto(int B, int Hkv, int kv_group, int Sq, int Sk);
 BF16_F32(void, attn_dropout_apply, void* x, int64_t BH, int64_t Sq, int64_t Sk, float p,
          uint64_t seed, hipStream_t stream);
 

@@ -17,7 +17,9 @@ Explicit re-design of the reference MultiheadAttention
   * opt-in flash routes, both off by default: ``flash_prefill`` sends the
     cached inference passes of a causal self-attention (prompt pass with
     ``use_cache``, multi-token step on a past) through the flash forward with
-    the past length as the query offset; ``flash_cross_attention`` sends the
+    the past length as the query offset (``"split"``: also the short chunks
+    on long caches that ``True`` leaves to the materialized route, through
+    the split-KV forward); ``flash_cross_attention`` sends the
     no-cache cross-attention call through the flash forward/backward on the
     packed key/value projection.
 """
@@ -85,7 +87,9 @@ class MultiheadAttention(nn.Module):
         super().__init__()
         # opt-in flash routes (both off: the layer is what it always was).
         # flash_prefill: the cached inference passes of a causal self-attention
-        # (prompt pass with use_cache, multi-token step on a past).
+        # (prompt pass with use_cache, multi-token step on a past).  "split"
+        # does what True does and also sends the chunk steps that True leaves
+        # to the materialized route (flash_chunk_pays) to the split-KV forward.
         # flash_cross_attention: the no-cache call of a cross-attention.
         self.flash_prefill = flash_prefill
         self.flash_cross_attention = flash_cross_attention
@@ -199,6 +203,7 @@ class MultiheadAttention(nn.Module):
             bias_rel_table,
             flash_chunk_pays,
             flash_prefill_available,
+            flash_split_keys,
             mask_kv_len,
         )
 
@@ -339,14 +344,23 @@ class MultiheadAttention(nn.Module):
         present = (k, v) if use_cache else None
 
         scale_d = self.norm_factor * (self.coeff if self.coeff else 1.0)
-        if (
+        chunk = (
             prefill
             and past_key_value is not None
             and q.shape[2] > 1
             and flash_prefill_available(self.head_size, q.dtype, q.device,
                                         q.shape[2], k.shape[2])
-            and flash_chunk_pays(q.shape[0], q.shape[1], q.shape[2], k.shape[2])
-        ):
+        )
+        # a few workgroups on a long cache: flash_prefill="split" sends the
+        # chunk to the split-KV forward where its policy accepts the shape
+        kv_split = None
+        if chunk and not flash_chunk_pays(q.shape[0], q.shape[1], q.shape[2],
+                                          k.shape[2]):
+            chunk = self.flash_prefill == "split" and flash_split_keys(
+                q.shape[0], k.shape[1], q.shape[1] // k.shape[1], q.shape[2],
+                k.shape[2]) > 0
+            kv_split = "auto"
+        if chunk:
             from ..ops.attention import flash_attention
 
             # a chunk behind the cache: query i sits at key past_len + i; the
@@ -355,7 +369,7 @@ class MultiheadAttention(nn.Module):
                 q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3),
                 scale_d, causal=True, training=False,
                 kv_len=mask_kv_len(attention_mask), alibi_slopes=slopes,
-                q_offset=past_key_value[0].shape[2],
+                q_offset=past_key_value[0].shape[2], kv_split=kv_split,
             )
             b, sq, nh, hs = o.shape
             out, bias = self.dense(o.reshape(b, sq, nh * hs))

@@ -18,6 +18,7 @@ from ..ops.attention import (
     flash_attention_available,
     flash_chunk_pays,
     flash_prefill_available,
+    flash_split_keys,
 )
 from ..ops.rope import apply_rotary_pos_emb
 from ..ops.softmax import fused_scale_mask_softmax
@@ -219,21 +220,30 @@ class LlamaAttention(nn.Module):
                 out, _ = self.o_proj(context)
                 out = out + residual if residual is not None else out
                 return (out, present) if use_cache else out
-            if (
+            chunk = (
                 self.flash_prefill
                 and past_key_value is not None
                 and s > 1
                 and flash_prefill_available(self.head_dim, q.dtype, q.device, s,
                                             kh.shape[2])
-                and flash_chunk_pays(b, self.num_heads_local, s, kh.shape[2])
-            ):
+            )
+            # a few workgroups on a long cache: flash_prefill="split" sends
+            # the chunk to the split-KV forward where its policy accepts it
+            kv_split = None
+            if chunk and not flash_chunk_pays(b, self.num_heads_local, s,
+                                              kh.shape[2]):
+                chunk = self.flash_prefill == "split" and flash_split_keys(
+                    b, self.num_kv_local, group, s, kh.shape[2]) > 0
+                kv_split = "auto"
+            if chunk:
                 # a chunk behind the cache: query i sits at key pos0 + i.  The
                 # kernel takes the head-major cache through [b, sk, kvh, hd]
                 # views and maps query heads to kv heads itself
                 o = flash_attention(q, kh.permute(0, 2, 1, 3),
                                     vh.permute(0, 2, 1, 3), self.scale,
                                     p_drop=0.0, causal=True, training=False,
-                                    window=window, q_offset=pos0)
+                                    window=window, q_offset=pos0,
+                                    kv_split=kv_split)
                 context = o.reshape(b, s, self.num_heads_local * self.head_dim)
                 out, _ = self.o_proj(context)
                 out = out + residual if residual is not None else out

@@ -45,6 +45,15 @@ only (no backward, no dropout); plain, ALiBi and window variants; the key
 count may be ragged.  ``q_offset = 0`` is the call it always was, top-left
 alignment for Sq != Sk included.
 
+Split-KV (a short chunk on a long cache): ``flash_attention(..., kv_split=n)``
+cuts the keys into splits of n keys (a multiple of 128) that run as separate
+workgroups, packs the query heads of a KV head into one tile (K and V are
+staged once per KV head) and folds the partial softmax states in a merge
+kernel.  ``kv_split="auto"`` asks the extension's policy
+(``flash_split_keys``) and keeps the single-pass kernel where it declines.
+Inference only, like ``q_offset`` (with which it composes; ``q_offset = 0``
+is allowed, causal or not): no dropout, no gradients, plain / ALiBi / window.
+
 Cross-attention (T5/MT5 decoder): ``flash_attention_kv`` takes the query
 projection and the packed [B, Sk, H, 2, D] key/value projection, non-causal,
 Sq != Sk; its backward writes dK and dV into one packed allocation.
@@ -61,7 +70,8 @@ from ._ext import draw_seed, ext
 
 __all__ = ["flash_attention", "flash_attention_qkv", "flash_attention_kv",
            "flash_attention_available", "flash_prefill_available",
-           "flash_cross_available", "flash_chunk_pays", "mask_kv_len", "bias_alibi_slopes",
+           "flash_cross_available", "flash_chunk_pays", "flash_split_keys",
+           "mask_kv_len", "bias_alibi_slopes",
            "bias_rel_table"]
 
 
@@ -199,6 +209,13 @@ def flash_chunk_pays(batch, heads, sq, sk):
     take the flash forward: not a few workgroups walking a long cache."""
     workgroups = batch * heads * -(-sq // 128)
     return sk < FLASH_CHUNK_LONG_CACHE or workgroups > FLASH_CHUNK_FEW_WORKGROUPS
+
+
+def flash_split_keys(batch, kv_heads, kv_group, sq, sk):
+    """The split-KV policy of the extension (``flash_split_keys_auto``, measured
+    in profiles/flash_split_chunk.md): keys per split for a chunk of sq queries
+    on sk keys, a multiple of 128, or 0 where splitting does not pay."""
+    return ext().flash_split_keys_auto(batch, kv_heads, kv_group, sq, sk)
 
 
 def flash_cross_available(head_dim, dtype, device, sq, sk, pad_mask):
@@ -347,9 +364,27 @@ def _check_q_offset(q_offset, sq, sk, causal, p_drop, rel_bias, doc_bounds):
                          f"({q_offset} + {sq} > {sk})")
 
 
+def _check_kv_split(kv_split, p_drop, rel_bias, doc_bounds, q, k, v):
+    """The rules of the split-KV path, before anything reaches the extension."""
+    if kv_split != "auto":
+        ok = isinstance(kv_split, int) and not isinstance(kv_split, bool)
+        if not ok or kv_split <= 0 or kv_split % 128 != 0:
+            raise ValueError(f"kv_split must be 'auto' or a positive multiple of "
+                             f"128, got {kv_split!r}")
+    if p_drop > 0:
+        raise ValueError("kv_split cannot be combined with dropout")
+    if rel_bias is not None:
+        raise ValueError("kv_split cannot be combined with rel_bias")
+    if doc_bounds is not None:
+        raise ValueError("kv_split cannot be combined with doc_bounds")
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad
+                                    or v.requires_grad):
+        raise ValueError("kv_split is an inference path: it has no backward")
+
+
 def flash_attention(q, k, v, scale, p_drop=0.0, causal=True, training=True,
                     kv_len=None, alibi_slopes=None, window=None, rel_bias=None,
-                    doc_bounds=None, q_offset=0):
+                    doc_bounds=None, q_offset=0, kv_split=None):
     """q, k, v: [B, S, H, D] bf16 -> O [B, S, H, D].
 
     alibi_slopes: optional fp32 [H] (query heads) — fused ALiBi bias.
@@ -365,13 +400,27 @@ def flash_attention(q, k, v, scale, p_drop=0.0, causal=True, training=True,
     q_offset: optional int n > 0 — query row i sits at key position n + i (a
     chunk behind n cached keys; n = Sk - Sq for a cat([past, new]) cache).
     Inference only: causal, no dropout, no gradients, plain / alibi_slopes /
-    window; Sk may be ragged.  0 = off."""
+    window; Sk may be ragged.  0 = off.
+    kv_split: None (off), an int n (splits of n keys, a positive multiple of
+    128) or "auto" (the measured policy; the single-pass kernel where it
+    declines) — the split-KV forward for a short chunk on a long cache.
+    Inference only, like q_offset: no dropout, no gradients, plain /
+    alibi_slopes / window; q_offset = 0 is allowed, causal or not."""
     q_offset = int(q_offset)
     p_drop = p_drop if training else 0.0
+    if kv_split is not None:
+        _check_kv_split(kv_split, p_drop, rel_bias, doc_bounds, q, k, v)
     _check_q_offset(q_offset, q.shape[1], k.shape[1], causal, p_drop, rel_bias,
                     doc_bounds)
     variant = _variant_args(k.shape[1], causal, alibi_slopes, window, rel_bias,
                             doc_bounds)
+    if kv_split == "auto":
+        kv_split = flash_split_keys(q.shape[0], k.shape[2], q.shape[2] // k.shape[2],
+                                    q.shape[1], k.shape[1]) or None
+    if kv_split is not None:
+        return ext().flash_fwd_split(q, k, v, scale, causal, kv_len,
+                                     variant.alibi_slopes, variant.window, q_offset,
+                                     kv_split)[0]
     if q_offset > 0:
         if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad
                                         or v.requires_grad):

@@ -7,6 +7,11 @@ form with 8 kv heads), prompt pass with use_cache at S in {512, 2048, 4096}.
 chunk: the same layers, a step of Sq in {2, 16, 128, 512} tokens on 4096
 cached keys.
 sweep: the chunk case at Sq in {16, 128} on {256, 512, 1024, 2048} cached keys.
+split: the chunk case three ways, Sq in {2, 16, 128, 512} on {1024, 2048, 4096}
+cached keys: flag off, the single-pass flash route (gate bypassed) and
+flash_prefill="split" with split_keys forced to 128, 256, 512 and 1024 and with
+the policy's own choice ("auto"; 0 = it declines and the materialized route
+runs).  profiles/flash_split_chunk.md.
 cross: a T5-base decoder cross-attention (hidden 768, 12 heads), forward +
 backward at the shapes of configs/t5_pretrain.py (b 16, 114 queries, 512
 keys), with and without dropout.
@@ -16,7 +21,7 @@ rounds that alternate the variants; median and min..max of the per-round
 means.  Peak memory is torch.cuda.max_memory_allocated over one call, minus
 what was allocated before it.  One JSON line per case.
 
-Usage (GPU box): python tools/prefill_cross_bench.py [all|prompt|chunk|sweep|cross]
+Usage (GPU box): python tools/prefill_cross_bench.py [all|prompt|chunk|sweep|split|cross]
 """
 import json
 import os
@@ -68,14 +73,14 @@ def report(tag, r):
     print(json.dumps(row), flush=True)
 
 
-def llama_pair(kvh):
+def llama_pair(kvh, flag=True):
     from libai_amd.models.llama import LlamaAttention
 
     init = torch.nn.init.xavier_normal_
     torch.manual_seed(0)
     off = LlamaAttention(4096, 32, 8192, init, init, num_key_value_heads=kvh)
     on = LlamaAttention(4096, 32, 8192, init, init, num_key_value_heads=kvh,
-                        flash_prefill=True)
+                        flash_prefill=flag)
     off = off.to(dev, torch.bfloat16).eval()
     on = on.to(dev, torch.bfloat16).eval()
     on.load_state_dict(off.state_dict())
@@ -87,37 +92,89 @@ which = sys.argv[1] if len(sys.argv) > 1 else "all"
 # was taken from: measure the flash route itself, gated shapes included
 import libai_amd.models.llama as _llama
 
+_gate = _llama.flash_chunk_pays
 _llama.flash_chunk_pays = lambda *a: True
-with torch.no_grad():
+
+
+def split_mode():
+    """Three settings of one layer and its weights, every call through the
+    same wrapper: MODE tells the two hooks the layers ask (the gate and the
+    policy) what to answer, so no setting pays Python work another does not."""
+    import libai_amd.ops.attention as _ops
+
+    policy = _ops.flash_split_keys
+    mode = {"n": None}  # "on" | a forced split_keys | None: the layer as shipped
+
+    def gate(*a):
+        n = mode["n"]
+        return _gate(*a) if n is None else n == "on"  # forced n: never "pays"
+
+    def keys(*a):
+        n = mode["n"]
+        return policy(*a) if n is None else n
+
+    _llama.flash_chunk_pays = gate
+    _llama.flash_split_keys = _ops.flash_split_keys = keys
+
+    def call(layer, n, x, past):
+        def f():
+            mode["n"] = n
+            return layer(x, past_key_value=past, use_cache=True)
+        return f
+
     for kvh in (32, 8):
         off, on = llama_pair(kvh)
-        if which in ("all", "prompt"):
-            for s in (512, 2048, 4096):
-                x = torch.randn(1, s, 4096, device=dev, dtype=torch.bfloat16)
-                r = timed({"off": lambda: off(x, use_cache=True),
-                           "on": lambda: on(x, use_cache=True)})
-                a = off(x, use_cache=True)[0].float()
-                b = on(x, use_cache=True)[0].float()
-                report(f"prompt kvh{kvh} S{s} relerr "
-                       f"{((a - b).abs().max() / a.abs().max()).item():.2e}", r)
-        if which in ("all", "chunk"):
-            past = tuple(torch.randn(1, kvh, 4096, 128, device=dev, dtype=torch.bfloat16)
+        split = llama_pair(kvh, "split")[1]
+        for sk in (1024, 2048, 4096):
+            past = tuple(torch.randn(1, kvh, sk, 128, device=dev, dtype=torch.bfloat16)
                          for _ in range(2))
             for sq in (2, 16, 128, 512):
                 x = torch.randn(1, sq, 4096, device=dev, dtype=torch.bfloat16)
-                r = timed({"off": lambda: off(x, past_key_value=past, use_cache=True),
-                           "on": lambda: on(x, past_key_value=past, use_cache=True)})
-                report(f"chunk kvh{kvh} Sq{sq} on 4096", r)
-        if which == "sweep":  # where the chunk route starts to lose: fewer keys
-            for sk in (256, 512, 1024, 2048):
-                past = tuple(torch.randn(1, kvh, sk, 128, device=dev,
-                                         dtype=torch.bfloat16) for _ in range(2))
-                for sq in (16, 128):
+                fns = {"off": call(off, "on", x, past), "on": call(on, "on", x, past)}
+                for n in (128, 256, 512, 1024):
+                    fns[f"split{n}"] = call(split, n, x, past)
+                fns["split_auto"] = call(split, None, x, past)
+                auto = policy(1, kvh, 32 // kvh, sq, sk + sq)
+                gated = not _gate(1, 32, sq, sk + sq)
+                report(f"split kvh{kvh} Sq{sq} on {sk} auto={auto} gated={gated}",
+                       timed(fns))
+        del off, on, split
+
+
+if which == "split":
+    with torch.no_grad():
+        split_mode()
+else:
+    with torch.no_grad():
+        for kvh in (32, 8):
+            off, on = llama_pair(kvh)
+            if which in ("all", "prompt"):
+                for s in (512, 2048, 4096):
+                    x = torch.randn(1, s, 4096, device=dev, dtype=torch.bfloat16)
+                    r = timed({"off": lambda: off(x, use_cache=True),
+                               "on": lambda: on(x, use_cache=True)})
+                    a = off(x, use_cache=True)[0].float()
+                    b = on(x, use_cache=True)[0].float()
+                    report(f"prompt kvh{kvh} S{s} relerr "
+                           f"{((a - b).abs().max() / a.abs().max()).item():.2e}", r)
+            if which in ("all", "chunk"):
+                past = tuple(torch.randn(1, kvh, 4096, 128, device=dev, dtype=torch.bfloat16)
+                             for _ in range(2))
+                for sq in (2, 16, 128, 512):
                     x = torch.randn(1, sq, 4096, device=dev, dtype=torch.bfloat16)
                     r = timed({"off": lambda: off(x, past_key_value=past, use_cache=True),
                                "on": lambda: on(x, past_key_value=past, use_cache=True)})
-                    report(f"chunk kvh{kvh} Sq{sq} on {sk}", r)
-        del off, on
+                    report(f"chunk kvh{kvh} Sq{sq} on 4096", r)
+            if which == "sweep":  # where the chunk route starts to lose: fewer keys
+                for sk in (256, 512, 1024, 2048):
+                    past = tuple(torch.randn(1, kvh, sk, 128, device=dev,
+                                             dtype=torch.bfloat16) for _ in range(2))
+                    for sq in (16, 128):
+                        x = torch.randn(1, sq, 4096, device=dev, dtype=torch.bfloat16)
+                        r = timed({"off": lambda: off(x, past_key_value=past, use_cache=True),
+                                   "on": lambda: on(x, past_key_value=past, use_cache=True)})
+                        report(f"chunk kvh{kvh} Sq{sq} on {sk}", r)
+            del off, on
 
 if which in ("all", "cross"):
     from libai_amd.layers import MultiheadAttention
