@@ -822,6 +822,109 @@ py::tuple flash_bwd(
   return py::make_tuple(dq, dk, dv);
 }
 
+// ---------------------------------------------------------------------------
+// Window attention (Swin): packed qkv [B_, N, 3, H, 32], dense fp32 bias
+// [H, N, N], optional additive fp32 mask [nW, N, N] (window w uses w % nW)
+// ---------------------------------------------------------------------------
+static WindowAttnArgs window_attn_args(const char* op, const torch::Tensor& qkv5,
+                                       const torch::Tensor& bias, const OptTensor& mask,
+                                       double scale) {
+  TORCH_CHECK(qkv5.is_cuda() && qkv5.scalar_type() == torch::kBFloat16, op,
+              ": qkv must be a bf16 device tensor");
+  TORCH_CHECK(qkv5.dim() == 5 && qkv5.size(2) == 3, op,
+              ": qkv must be [B_, N, 3, H, 32]");
+  const int64_t B_ = qkv5.size(0), N = qkv5.size(1), H = qkv5.size(3);
+  TORCH_CHECK(qkv5.size(4) == 32, op, ": head size must be 32, got ", qkv5.size(4));
+  TORCH_CHECK(N >= 1 && N <= 64, op, ": 1 <= N <= 64 tokens per window, got ", N);
+  // grid limits: (B_ * H) / 4 workgroups forward, (H, slices) backward
+  TORCH_CHECK(B_ >= 1 && H >= 1 && H <= 65535 && B_ < (int64_t)1 << 31 &&
+                  B_ * H < (int64_t)1 << 33,
+              op, ": empty or oversized qkv");
+  TORCH_CHECK(qkv5.stride(4) == 1 && qkv5.stride(0) % 8 == 0 && qkv5.stride(1) % 8 == 0 &&
+                  qkv5.stride(2) % 8 == 0 && qkv5.stride(3) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(qkv5.data_ptr()) % 16 == 0,
+              op, ": qkv needs a contiguous last dim and 16-byte aligned rows");
+  auto f32_on = [&](const torch::Tensor& t) {
+    return t.is_cuda() && t.get_device() == qkv5.get_device() &&
+           t.scalar_type() == torch::kFloat32 && t.is_contiguous();
+  };
+  TORCH_CHECK(f32_on(bias) && bias.dim() == 3 && bias.size(0) == H && bias.size(1) == N &&
+                  bias.size(2) == N,
+              op, ": bias must be a contiguous fp32 [H, N, N] tensor on qkv's device");
+  WindowAttnArgs a{};
+  a.nW = 1;
+  if (mask.has_value()) {
+    const torch::Tensor& m = mask.value();
+    TORCH_CHECK(f32_on(m) && m.dim() == 3 && m.size(0) >= 1 && m.size(1) == N &&
+                    m.size(2) == N,
+                op, ": mask must be a contiguous fp32 [nW, N, N] tensor on qkv's device");
+    TORCH_CHECK(B_ % m.size(0) == 0, op, ": B_ = ", B_,
+                " is not a multiple of the mask's nW = ", m.size(0));
+    a.mask = m.data_ptr<float>();
+    a.nW = (int)m.size(0);
+  }
+  a.qkv = qkv5.data_ptr();
+  a.s_b = qkv5.stride(0);
+  a.s_n = qkv5.stride(1);
+  a.s_3 = qkv5.stride(2);
+  a.s_h = qkv5.stride(3);
+  a.bias = bias.data_ptr<float>();
+  a.B_ = (int)B_;
+  a.N = (int)N;
+  a.H = (int)H;
+  a.scale = (float)scale;
+  return a;
+}
+
+std::tuple<torch::Tensor, torch::Tensor> window_attn_fwd(torch::Tensor qkv5,
+                                                         torch::Tensor bias,
+                                                         OptTensor mask, double scale) {
+  WindowAttnArgs a = window_attn_args("window_attn_fwd", qkv5, bias, mask, scale);
+  auto o = torch::empty({a.B_, a.N, a.H, 32}, qkv5.options());
+  auto lse = torch::empty({a.B_, a.H, a.N}, qkv5.options().dtype(torch::kFloat32));
+  a.o = o.data_ptr();
+  a.lse = lse.data_ptr<float>();
+  window_attn_fwd_bf16(a, cur_stream());
+  check_launch("window_attn_fwd");
+  return {o, lse};
+}
+
+// dbias_slices: workgroups per head = slices of the fp32 partial buffer the
+// bias gradient is folded from; 0 lets the launcher choose.
+std::tuple<torch::Tensor, torch::Tensor> window_attn_bwd(
+    torch::Tensor qkv5, torch::Tensor o, torch::Tensor dout, torch::Tensor lse,
+    torch::Tensor bias, OptTensor mask, double scale, int64_t dbias_slices) {
+  WindowAttnBwdArgs a{};
+  static_cast<WindowAttnArgs&>(a) =
+      window_attn_args("window_attn_bwd", qkv5, bias, mask, scale);
+  auto like_o = [&](const torch::Tensor& t) {
+    return t.is_cuda() && t.get_device() == qkv5.get_device() &&
+           t.scalar_type() == torch::kBFloat16 && t.is_contiguous() && t.dim() == 4 &&
+           t.size(0) == a.B_ && t.size(1) == a.N && t.size(2) == a.H && t.size(3) == 32;
+  };
+  TORCH_CHECK(like_o(o) && like_o(dout),
+              "window_attn_bwd: o and dout must be contiguous bf16 [B_, N, H, 32]");
+  TORCH_CHECK(lse.is_cuda() && lse.get_device() == qkv5.get_device() &&
+                  lse.scalar_type() == torch::kFloat32 && lse.is_contiguous() &&
+                  lse.dim() == 3 && lse.size(0) == a.B_ && lse.size(1) == a.H &&
+                  lse.size(2) == a.N,
+              "window_attn_bwd: lse must be contiguous fp32 [B_, H, N]");
+  TORCH_CHECK(dbias_slices >= 0 && dbias_slices <= 65535,
+              "window_attn_bwd: dbias_slices must be in [0, 65535]");
+  a.P = dbias_slices > 0 ? (int)dbias_slices : window_attn_bwd_slices(a.B_, a.H, a.N);
+  auto dqkv = torch::empty({a.B_, a.N, 3, a.H, 32}, qkv5.options());
+  auto partial =
+      torch::empty({a.P, a.H, a.N, a.N}, qkv5.options().dtype(torch::kFloat32));
+  a.o = o.data_ptr();
+  a.lse = lse.data_ptr<float>();
+  a.dout = dout.data_ptr();
+  a.dqkv = dqkv.data_ptr();
+  a.dbias_partial = partial.data_ptr<float>();
+  window_attn_bwd_bf16(a, cur_stream());
+  check_launch("window_attn_bwd");
+  return {dqkv, a.P == 1 ? partial.squeeze(0) : partial.sum(0)};
+}
+
 void attn_dropout_apply(torch::Tensor x, int64_t Sq, int64_t Sk, double p,
                         int64_t seed) {
   CHECK_IN(x);
@@ -1023,6 +1126,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kv_len"), py::arg("alibi_slopes") = py::none(), py::arg("window") = 0,
         py::arg("rel_bias") = py::none(), py::arg("doc_start") = py::none(),
         py::arg("doc_end") = py::none(), py::arg("dkv") = py::none());
+  m.def("window_attn_fwd", &window_attn_fwd, py::arg("qkv5"), py::arg("bias"),
+        py::arg("mask"), py::arg("scale"));
+  m.def("window_attn_bwd", &window_attn_bwd, py::arg("qkv5"), py::arg("o"),
+        py::arg("dout"), py::arg("lse"), py::arg("bias"), py::arg("mask"),
+        py::arg("scale"), py::arg("dbias_slices") = 0);
   m.def("attn_dropout_apply", &attn_dropout_apply);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);

@@ -54,6 +54,28 @@ struct FlashSplitArgs : FlashFwdArgs {
   int split_keys;          // a positive multiple of 128
 };
 
+// ---------------------------------------------------------------------------
+// window attention (window_attn.hip): Swin windows, head size 32, N <= 64
+// ---------------------------------------------------------------------------
+struct WindowAttnArgs {
+  const void* qkv;  // bf16 [B_, N, 3, H, 32], last dim contiguous
+  int64_t s_b, s_n, s_3, s_h;  // its strides in elements (multiples of 8)
+  const float* bias;  // [H, N, N], indexed [h][query][key]
+  const float* mask;  // [nW, N, N] additive, window w uses mask[w % nW]; or null
+  int B_, N, H, nW;   // nW = 1 without a mask
+  float scale;
+  void* o;     // bf16 [B_, N, H, 32] contiguous: written by the forward
+  float* lse;  // [B_, H, N]: written by the forward, read by the backward
+};
+
+struct WindowAttnBwdArgs : WindowAttnArgs {
+  const void* dout;      // o's layout
+  void* dqkv;            // bf16 [B_, N, 3, H, 32] contiguous
+  float* dbias_partial;  // [P, H, N, N]: slice p holds the sums of the windows
+                         // of workgroup (h, p); every element is written
+  int P;                 // 1 <= P <= 65535
+};
+
 // NAME_bf16 and NAME_f32 with one parameter list (the .hip files define the
 // pairs from one macro body too)
 #define BF16_F32(RET, NAME, ...) \
@@ -87,6 +109,13 @@ void flash_decode_split_bf16(const void* q, const void* k, const void* v, void* 
                              int B, int H, int S, int Skv, int D, float scale,
                              int kv_group, const float* alibi_slopes, int window,
                              hipStream_t stream);
+
+// window_attn.hip
+void window_attn_fwd_bf16(const WindowAttnArgs& args, hipStream_t stream);
+void window_attn_bwd_bf16(const WindowAttnBwdArgs& args, hipStream_t stream);
+// dbias slices (workgroups per head) the backward picks for B_ windows of N
+// tokens on the current device
+int window_attn_bwd_slices(int B_, int H, int N);
 
 // layer_norm.hip
 BF16_F32(void, ln_fwd, const void* x, const void* gamma, const void* beta, void* y,

@@ -12,6 +12,7 @@ from torch import nn
 
 from ..config import configurable
 from ..layers import DropPath, build_activation
+from ..ops.attention import window_attention, window_attention_available
 from .utils.weight_init import init_method_normal
 
 __all__ = ["SwinTransformer"]
@@ -31,8 +32,13 @@ def window_reverse(windows, ws, H, W):
 
 class WindowAttention(nn.Module):
     def __init__(self, dim, window_size, num_heads, qkv_bias=True, attn_drop=0.0,
-                 proj_drop=0.0):
+                 proj_drop=0.0, fused_window_attention=False):
         super().__init__()
+        # one HIP kernel for scores, bias, shift mask, softmax and PV where the
+        # op serves the shape (bf16 on the GPU, head size 32, N <= 64, no
+        # active attention dropout); it adds the bias in fp32 where the
+        # materialized path adds it in bf16, so it is opt-in
+        self.fused_window_attention = fused_window_attention
         self.dim = dim
         self.window_size = window_size
         self.num_heads = num_heads
@@ -61,6 +67,19 @@ class WindowAttention(nn.Module):
 
     def forward(self, x, mask=None):
         B_, N, C = x.shape
+        if (
+            self.fused_window_attention
+            and not (self.training and self.attn_drop.p > 0)
+            and window_attention_available(C // self.num_heads, N, x.dtype, x.device)
+        ):
+            qkv5 = self.qkv(x).reshape(B_, N, 3, self.num_heads, C // self.num_heads)
+            # fp32 gather: autograd carries dbias back to the table through it
+            bias = self.relative_position_bias_table.float()[
+                self.relative_position_index.view(-1)
+            ].view(N, N, -1).permute(2, 0, 1).contiguous()
+            x = window_attention(qkv5, bias, self.scale,
+                                 mask=None if mask is None else mask.float())
+            return self.proj_drop(self.proj(x))
         qkv = (
             self.qkv(x)
             .reshape(B_, N, 3, self.num_heads, C // self.num_heads)
@@ -87,7 +106,7 @@ class WindowAttention(nn.Module):
 class SwinBlock(nn.Module):
     def __init__(self, dim, input_resolution, num_heads, window_size=7, shift_size=0,
                  mlp_ratio=4.0, qkv_bias=True, drop=0.0, attn_drop=0.0,
-                 drop_path=0.0, *, layer_idx=0):
+                 drop_path=0.0, *, layer_idx=0, fused_window_attention=False):
         super().__init__()
         self.dim = dim
         self.input_resolution = input_resolution
@@ -97,7 +116,8 @@ class SwinBlock(nn.Module):
 
         self.norm1 = nn.LayerNorm(dim)
         self.attn = WindowAttention(dim, self.window_size, num_heads, qkv_bias,
-                                    attn_drop, drop)
+                                    attn_drop, drop,
+                                    fused_window_attention=fused_window_attention)
         self.drop_path = DropPath(drop_path)
         self.norm2 = nn.LayerNorm(dim)
         hidden = int(dim * mlp_ratio)
@@ -167,7 +187,8 @@ class SwinTransformer(nn.Module):
     def __init__(self, img_size=224, patch_size=4, in_chans=3, num_classes=1000,
                  embed_dim=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24),
                  window_size=7, mlp_ratio=4.0, qkv_bias=True, drop_rate=0.0,
-                 attn_drop_rate=0.0, drop_path_rate=0.1, loss_func=None):
+                 attn_drop_rate=0.0, drop_path_rate=0.1, loss_func=None,
+                 fused_window_attention=False):
         super().__init__()
         self.num_classes = num_classes
         self.num_layers = len(depths)
@@ -191,6 +212,7 @@ class SwinTransformer(nn.Module):
                         mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, drop=drop_rate,
                         attn_drop=attn_drop_rate, drop_path=dpr[li + j],
                         layer_idx=li + j,
+                        fused_window_attention=fused_window_attention,
                     )
                     for j in range(depth)
                 ]
@@ -222,6 +244,7 @@ class SwinTransformer(nn.Module):
             "attn_drop_rate": cfg.get("attn_drop_rate", 0.0),
             "drop_path_rate": cfg.get("drop_path_rate", 0.1),
             "loss_func": cfg.get("loss_func", None),
+            "fused_window_attention": cfg.get("fused_window_attention", False),
         }
 
     def forward_features(self, x):

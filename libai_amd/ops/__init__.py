@@ -1,5 +1,10 @@
 from ._ext import draw_seed, ext, has_ext, use_hip
-from .attention import flash_attention, flash_attention_available
+from .attention import (
+    flash_attention,
+    flash_attention_available,
+    window_attention,
+    window_attention_available,
+)
 from .cross_entropy import vocab_parallel_cross_entropy
 from .fused_bias import bias_dropout_add, bias_gelu
 from .norm import (
@@ -27,6 +32,8 @@ __all__ = [
     "vocab_parallel_cross_entropy",
     "flash_attention",
     "flash_attention_available",
+    "window_attention",
+    "window_attention_available",
     "apply_rotary_pos_emb",
     "RotaryEmbedding",
     "swiglu",

@@ -58,6 +58,12 @@ Cross-attention (T5/MT5 decoder): ``flash_attention_kv`` takes the query
 projection and the packed [B, Sk, H, 2, D] key/value projection, non-causal,
 Sq != Sk; its backward writes dK and dV into one packed allocation.
 
+Window attention (Swin): ``window_attention`` takes the packed
+``[B_, N, 3, H, 32]`` projection of windows of N <= 64 tokens, a dense fp32
+``[H, N, N]`` bias and an optional additive fp32 ``[nW, N, N]`` shift mask; one
+wave per (window, head), forward and a single backward kernel that also yields
+the bias gradient (libai_amd/csrc/kernels/window_attn.hip).
+
 Replaces the reference's K2-K5 chain (reference
 libai/layers/attention.py:211-253).
 """
@@ -72,7 +78,7 @@ __all__ = ["flash_attention", "flash_attention_qkv", "flash_attention_kv",
            "flash_attention_available", "flash_prefill_available",
            "flash_cross_available", "flash_chunk_pays", "flash_split_keys",
            "mask_kv_len", "bias_alibi_slopes",
-           "bias_rel_table"]
+           "bias_rel_table", "window_attention", "window_attention_available"]
 
 
 def mask_kv_len(pad_mask):
@@ -456,3 +462,84 @@ def flash_decode_attn(q, k, v, scale, kv_len=None, alibi_slopes=None,
     variant = _variant_args(k.shape[2], True, alibi_slopes, window)
     return ext().flash_decode(q, k, v, scale, kv_len, variant.alibi_slopes,
                               variant.window)
+
+
+# ---------------------------------------------------------------------------
+# window attention (Swin)
+# ---------------------------------------------------------------------------
+WINDOW_HEAD_DIM = 32
+WINDOW_MAX_TOKENS = 64
+
+
+def window_attention_available(head_dim, n_tokens, dtype, device):
+    """Whether ``window_attention`` serves windows of n_tokens tokens with heads
+    of head_dim.  Every stage shape of the shipped Swin recipe measured faster
+    than the materialized route (profiles/window_attn.md), so no shape inside
+    the kernel's range is declined."""
+    return (
+        device.type == "cuda"
+        and dtype == torch.bfloat16
+        and head_dim == WINDOW_HEAD_DIM
+        and 1 <= n_tokens <= WINDOW_MAX_TOKENS
+    )
+
+
+def _check_window_args(qkv5, bias, mask):
+    if qkv5.dim() != 5 or qkv5.shape[2] != 3:
+        raise ValueError(f"qkv must be [B_, N, 3, H, 32], got {tuple(qkv5.shape)}")
+    b_, n, _, h, d = qkv5.shape
+    if d != WINDOW_HEAD_DIM:
+        raise ValueError(f"window_attention serves head size 32, got {d}")
+    if not 1 <= n <= WINDOW_MAX_TOKENS:
+        raise ValueError(f"window_attention serves 1 <= N <= 64 tokens, got {n}")
+    if qkv5.dtype != torch.bfloat16:
+        raise ValueError(f"window_attention is bf16-only, got {qkv5.dtype}")
+    if bias.dtype != torch.float32 or tuple(bias.shape) != (h, n, n):
+        raise ValueError(
+            f"bias must be fp32 [H, N, N] = {(h, n, n)}, got {bias.dtype} "
+            f"{tuple(bias.shape)}")
+    if mask is not None:
+        if mask.dtype != torch.float32 or mask.dim() != 3 or \
+                tuple(mask.shape[1:]) != (n, n) or mask.shape[0] < 1:
+            raise ValueError(
+                f"mask must be fp32 [nW, N, N], got {mask.dtype} {tuple(mask.shape)}")
+        if b_ % mask.shape[0] != 0:
+            raise ValueError(
+                f"B_ = {b_} is not a multiple of the mask's nW = {mask.shape[0]}")
+
+
+class _WindowAttnFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv5, bias, mask, scale, dbias_slices):
+        o, lse = ext().window_attn_fwd(qkv5, bias, mask, scale)
+        ctx.save_for_backward(qkv5, bias, o, lse)
+        ctx.mask = mask
+        ctx.meta = (scale, dbias_slices)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv5, bias, o, lse = ctx.saved_tensors
+        scale, dbias_slices = ctx.meta
+        dqkv, dbias = ext().window_attn_bwd(qkv5, o, do.contiguous(), lse, bias,
+                                            ctx.mask, scale, dbias_slices or 0)
+        return dqkv, dbias, None, None, None
+
+
+def window_attention(qkv5, bias, scale, mask=None, dbias_slices=None):
+    """qkv5: packed [B_, N, 3, H, 32] bf16 (read through its strides) ->
+    [B_, N, H * 32], the softmax(scale * q k^T + bias + mask) v of every
+    (window, head).
+
+    bias: fp32 [H, N, N], indexed [head][query][key]; differentiable.
+    mask: optional fp32 [nW, N, N] of finite additive values; window w uses
+    mask[w % nW] and B_ must be a multiple of nW.  No gradient.
+    dbias_slices: workgroups per head of the backward, each of which leaves
+    one fp32 partial of the bias gradient (None: chosen from B_ and the chip)."""
+    _check_window_args(qkv5, bias, mask)
+    if dbias_slices is not None and not 1 <= dbias_slices <= 65535:
+        raise ValueError(f"dbias_slices must be in [1, 65535], got {dbias_slices}")
+    if mask is not None:
+        mask = mask.detach().contiguous()
+    o = _WindowAttnFn.apply(qkv5, bias.contiguous(), mask, scale, dbias_slices)
+    return o.view(o.shape[0], o.shape[1], -1)
