@@ -192,6 +192,43 @@ __device__ __forceinline__ void stage_tile(bf16_t* row_lds, bf16_t* tr_lds,
   }
 }
 
+// stage_tile in two halves, for the round loops of flash_fwd and flash_bwd_q.
+// stage_tile's `(gr < bound) ? load : 0` puts every 16-byte chunk into an exec
+// region of its own, load -> s_waitcnt vmcnt(0) -> ds_write: one dependent
+// global round trip per chunk.  load_rows issues all chunks of a [ROWS][D]
+// tile into registers and waits for none; every load is unconditional, its
+// row clamped to bound - 1 (bound >= 1: no row past the tensor is ever read).
+// write_rows selects zeros for the rows >= bound and stores the same LDS
+// images as stage_tile; the counted waits land in front of its ds_writes.
+template <int ROWS, int D>
+__device__ __forceinline__ void load_rows(bf16x8_t (&regs)[ROWS * D / 8 / 256],
+                                          const bf16_t* gp, int row0, int bound,
+                                          int64_t stride, int tid) {
+  static_assert(ROWS * D / 8 % 256 == 0, "whole chunks per thread");
+#pragma unroll
+  for (int cc = 0; cc < ROWS * D / 8 / 256; ++cc) {
+    const int flat = tid + cc * 256;
+    const int gr = min(row0 + flat / (D / 8), bound - 1);
+    const int col8 = flat % (D / 8);
+    regs[cc] = *(const bf16x8_t*)(gp + (int64_t)gr * stride + col8 * 8);
+  }
+}
+
+template <int ROWS, int D, bool ROW_IMG, bool TR_IMG>
+__device__ __forceinline__ void write_rows(
+    const bf16x8_t (&regs)[ROWS * D / 8 / 256], bf16_t* row_lds, bf16_t* tr_lds,
+    int row0, int bound, int tid) {
+#pragma unroll
+  for (int cc = 0; cc < ROWS * D / 8 / 256; ++cc) {
+    const int flat = tid + cc * 256;
+    const int row = flat / (D / 8);
+    const int col8 = flat % (D / 8);
+    const bf16x8_t val = (row0 + row < bound) ? regs[cc] : bf16x8_t{};
+    if (ROW_IMG) row_img_write<D>(row_lds, row, col8, val);
+    if (TR_IMG) tr_img_write<D>(tr_lds, row, col8 * 8, val);
+  }
+}
+
 // Attention dropout: ONE 32-bit hash keyed on (bh, q, kv>>2) yields four
 // byte-granular keep decisions (kv&3 selects the byte; p quantized to 1/256,
 // well below dropout's statistical resolution).  The forward and dQ backward
@@ -432,8 +469,13 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void flash_fwd_kernel(
   for (int round = round0; round < n_rounds; ++round) {
     const int kvR = round * 2 * KVB;
     __syncthreads();
-    stage_tile<2 * KVB, D, true, false>(k_lds, nullptr, kp, kvR, Sk, k_ss, tid);
-    stage_tile<2 * KVB, D, false, true>(nullptr, v_lds, vp, kvR, Sk, v_ss, tid);
+    {  // all K and V loads of the round in flight, then all LDS stores
+      bf16x8_t k_st[2 * KVB * D / 8 / 256], v_st[2 * KVB * D / 8 / 256];
+      load_rows<2 * KVB, D>(k_st, kp, kvR, Sk, k_ss, tid);
+      load_rows<2 * KVB, D>(v_st, vp, kvR, Sk, v_ss, tid);
+      write_rows<2 * KVB, D, true, false>(k_st, k_lds, nullptr, kvR, Sk, tid);
+      write_rows<2 * KVB, D, false, true>(v_st, nullptr, v_lds, kvR, Sk, tid);
+    }
     if constexpr (RELB) {
       if (tid < FWD_DIAGS)
         rb_lds[tid] =
@@ -1533,8 +1575,13 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_q_kernel(
   for (int tile = tile0; tile < n_tiles; ++tile) {
     const int kv0 = tile * KVTILE;
     __syncthreads();
-    stage_tile<KVTILE, D, true, true>(k_row, k_tr, kp, kv0, Sk, k_ss, tid);
-    stage_tile<KVTILE, D, true, false>(v_row, nullptr, vp, kv0, Sk, v_ss, tid);
+    {  // all K and V loads of the tile in flight, then all LDS stores
+      bf16x8_t k_st[KVTILE * D / 8 / 256], v_st[KVTILE * D / 8 / 256];
+      load_rows<KVTILE, D>(k_st, kp, kv0, Sk, k_ss, tid);
+      load_rows<KVTILE, D>(v_st, vp, kv0, Sk, v_ss, tid);
+      write_rows<KVTILE, D, true, true>(k_st, k_row, k_tr, kv0, Sk, tid);
+      write_rows<KVTILE, D, true, false>(v_st, v_row, nullptr, kv0, Sk, tid);
+    }
     if constexpr (RELB) {
       if (tile > tile0)  // the diagonals the previous tile completed
         relb_flush(drb_lds, drbp, tid, KVTILE, kv0 - KVTILE, rb_t0, n_diag);
