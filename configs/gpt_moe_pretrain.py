@@ -10,6 +10,9 @@ from .gpt2_pretrain import dataloader, gpt_cfg, model, optim, train  # noqa: F40
 
 gpt_cfg.moe_num_experts = 8  # must be divisible by the DP(=EP) size
 gpt_cfg.moe_top_k = 2
+# HIP routing / dispatch / combine (ops/moe.py); off until a training-curve
+# comparison: the fused combine sums in fp32 and rounds once
+gpt_cfg.moe_fused_dispatch = False
 
 train.scheduler = LazyCall(WarmupCosineLR)(
     max_iter=1000,

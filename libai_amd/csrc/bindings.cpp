@@ -1065,6 +1065,163 @@ torch::Tensor swiglu_bwd(torch::Tensor x, torch::Tensor dy) {
 }
 
 // ---------------------------------------------------------------------------
+// MoE routing, dispatch and combine (moe.hip)
+// ---------------------------------------------------------------------------
+namespace {
+
+void check_moe_k(const char* op, int64_t n, int64_t E, int64_t k) {
+  TORCH_CHECK(E >= 1 && E <= 256, op, ": 1 <= E <= 256, got ", E);
+  TORCH_CHECK(k >= 1 && k <= 8 && k <= E, op, ": 1 <= k <= min(E, 8), got k = ", k,
+              " with E = ", E);
+  TORCH_CHECK(n >= 1 && n * k < (int64_t(1) << 31), op, ": 1 <= n and n * k < 2^31");
+}
+
+// rows [R, H] of bf16 / fp32 in whole 16-byte vectors
+void check_moe_rows(const char* op, const torch::Tensor& t, int64_t R) {
+  CHECK_IN(t);
+  is_bf16(t);
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == R, op, ": expected [", R, ", H] rows");
+  TORCH_CHECK(t.size(1) > 0 && (t.size(1) * t.element_size()) % 16 == 0, op,
+              ": row width ", t.size(1), " is not a multiple of 16 bytes");
+}
+
+void check_moe_index(const char* op, const torch::Tensor& t, int64_t numel) {
+  CHECK_IN(t);
+  TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.numel() == numel, op,
+              ": index tensor must be int32 with ", numel, " elements");
+}
+
+void check_moe_f32(const char* op, const torch::Tensor& t, int64_t numel) {
+  CHECK_IN(t);
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.numel() == numel, op,
+              ": expected an fp32 tensor with ", numel, " elements");
+}
+
+}  // namespace
+
+// -> gates [n,k] f32, idx [n,k] i32, counts [E] i32, psum [E] f32,
+//    slot [n*k] i32, row_of_slot [n*k] i32, expert_offsets [E+1] i32
+std::vector<torch::Tensor> moe_route(torch::Tensor logits, int64_t k) {
+  CHECK_IN(logits);
+  TORCH_CHECK(logits.scalar_type() == torch::kFloat32 && logits.dim() == 2,
+              "moe_route: logits must be fp32 [n, E]");
+  const int64_t n = logits.size(0), E = logits.size(1);
+  check_moe_k("moe_route", n, E, k);
+  auto f32 = logits.options();
+  auto i32 = logits.options().dtype(torch::kInt32);
+  const int64_t nblocks = (n + moe_tokens_per_block(n) - 1) / moe_tokens_per_block(n);
+  auto gates = torch::empty({n, k}, f32);
+  auto idx = torch::empty({n, k}, i32);
+  auto hist = torch::empty({nblocks, E}, i32);
+  auto psum_part = torch::empty({nblocks, E}, f32);
+  auto counts = torch::empty({E}, i32);
+  auto offsets = torch::empty({E + 1}, i32);
+  auto psum = torch::empty({E}, f32);
+  auto slot = torch::empty({n * k}, i32);
+  auto row_of_slot = torch::empty({n * k}, i32);
+  moe_route_f32(logits.data_ptr<float>(), gates.data_ptr<float>(), idx.data_ptr<int>(),
+                hist.data_ptr<int>(), psum_part.data_ptr<float>(),
+                counts.data_ptr<int>(), offsets.data_ptr<int>(),
+                psum.data_ptr<float>(), slot.data_ptr<int>(),
+                row_of_slot.data_ptr<int>(), (int)n, (int)E, (int)k, cur_stream());
+  check_launch("moe_route");
+  return {gates, idx, counts, psum, slot, row_of_slot, offsets};
+}
+
+torch::Tensor moe_route_bwd(torch::Tensor logits, torch::Tensor idx,
+                            torch::Tensor gates, torch::Tensor dgates,
+                            torch::Tensor dpsum) {
+  CHECK_IN(logits);
+  TORCH_CHECK(logits.scalar_type() == torch::kFloat32 && logits.dim() == 2,
+              "moe_route_bwd: logits must be fp32 [n, E]");
+  TORCH_CHECK(idx.dim() == 2, "moe_route_bwd: idx must be [n, k]");
+  const int64_t n = logits.size(0), E = logits.size(1), k = idx.size(1);
+  check_moe_k("moe_route_bwd", n, E, k);
+  check_moe_index("moe_route_bwd", idx, n * k);
+  check_moe_f32("moe_route_bwd", gates, n * k);
+  check_moe_f32("moe_route_bwd", dgates, n * k);
+  check_moe_f32("moe_route_bwd", dpsum, E);
+  auto dlogits = torch::empty_like(logits);
+  moe_route_bwd_f32(logits.data_ptr<float>(), idx.data_ptr<int>(),
+                    gates.data_ptr<float>(), dgates.data_ptr<float>(),
+                    dpsum.data_ptr<float>(), dlogits.data_ptr<float>(), (int)n, (int)E,
+                    (int)k, cur_stream());
+  check_launch("moe_route_bwd");
+  return dlogits;
+}
+
+// xk[s] = x[row_of_slot[s] / k]
+torch::Tensor moe_permute(torch::Tensor x, torch::Tensor row_of_slot, int64_t k) {
+  TORCH_CHECK(x.dim() == 2, "moe_permute: x must be [n, H]");
+  const int64_t n = x.size(0), H = x.size(1);
+  check_moe_k("moe_permute", n, 256, k);
+  check_moe_rows("moe_permute", x, n);
+  check_moe_index("moe_permute", row_of_slot, n * k);
+  auto xk = torch::empty({n * k, H}, x.options());
+  auto fn = is_bf16(x) ? moe_permute_bf16 : moe_permute_f32;
+  fn(x.data_ptr(), row_of_slot.data_ptr<int>(), xk.data_ptr(), (int)n, (int)k, (int)H,
+     cur_stream());
+  check_launch("moe_permute");
+  return xk;
+}
+
+// y[i] = sum_j gates[i,j] * yk[slot[i*k+j]] (+ residual[i]); without gates the
+// unweighted sum
+torch::Tensor moe_combine(torch::Tensor yk, c10::optional<torch::Tensor> gates,
+                          torch::Tensor slot, c10::optional<torch::Tensor> residual,
+                          int64_t k) {
+  TORCH_CHECK(yk.dim() == 2 && k >= 1 && yk.size(0) % k == 0,
+              "moe_combine: yk must be [n * k, H]");
+  const int64_t n = yk.size(0) / k, H = yk.size(1);
+  check_moe_k("moe_combine", n, 256, k);
+  check_moe_rows("moe_combine", yk, n * k);
+  check_moe_index("moe_combine", slot, n * k);
+  const float* gptr = nullptr;
+  if (gates.has_value()) {
+    check_moe_f32("moe_combine", *gates, n * k);
+    gptr = gates->data_ptr<float>();
+  }
+  const void* rptr = nullptr;
+  if (residual.has_value()) {
+    check_moe_rows("moe_combine", *residual, n);
+    TORCH_CHECK(residual->size(1) == H && residual->scalar_type() == yk.scalar_type(),
+                "moe_combine: residual must match yk's width and dtype");
+    rptr = residual->data_ptr();
+  }
+  auto y = torch::empty({n, H}, yk.options());
+  auto fn = is_bf16(yk) ? moe_combine_bf16 : moe_combine_f32;
+  fn(yk.data_ptr(), gptr, slot.data_ptr<int>(), rptr, y.data_ptr(), (int)n, (int)k,
+     (int)H, cur_stream());
+  check_launch("moe_combine");
+  return y;
+}
+
+// -> dyk [n*k, H], dgates [n, k] f32
+std::tuple<torch::Tensor, torch::Tensor> moe_combine_bwd(torch::Tensor dy,
+                                                         torch::Tensor yk,
+                                                         torch::Tensor gates,
+                                                         torch::Tensor row_of_slot,
+                                                         int64_t k) {
+  TORCH_CHECK(dy.dim() == 2, "moe_combine_bwd: dy must be [n, H]");
+  const int64_t n = dy.size(0), H = dy.size(1);
+  check_moe_k("moe_combine_bwd", n, 256, k);
+  check_moe_rows("moe_combine_bwd", dy, n);
+  check_moe_rows("moe_combine_bwd", yk, n * k);
+  TORCH_CHECK(yk.size(1) == H && yk.scalar_type() == dy.scalar_type(),
+              "moe_combine_bwd: yk must match dy's width and dtype");
+  check_moe_f32("moe_combine_bwd", gates, n * k);
+  check_moe_index("moe_combine_bwd", row_of_slot, n * k);
+  auto dyk = torch::empty_like(yk);
+  auto dgates = torch::empty({n, k}, gates.options());
+  auto fn = is_bf16(dy) ? moe_combine_bwd_bf16 : moe_combine_bwd_f32;
+  fn(dy.data_ptr(), yk.data_ptr(), gates.data_ptr<float>(),
+     row_of_slot.data_ptr<int>(), dyk.data_ptr(), dgates.data_ptr<float>(), (int)n,
+     (int)k, (int)H, cur_stream());
+  check_launch("moe_combine_bwd");
+  return {dyk, dgates};
+}
+
+// ---------------------------------------------------------------------------
 // fused AdamW
 // ---------------------------------------------------------------------------
 void adamw_step(torch::Tensor chunks, bool bf16_params, double lr, double beta1,
@@ -1141,6 +1298,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("res_norm_fwd", &res_norm_fwd);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
+  m.def("moe_route", &moe_route);
+  m.def("moe_route_bwd", &moe_route_bwd);
+  m.def("moe_permute", &moe_permute);
+  m.def("moe_combine", &moe_combine);
+  m.def("moe_combine_bwd", &moe_combine_bwd);
   m.def("adamw_step", &adamw_step);
   m.def("l2norm_sq", &l2norm_sq);
   m.def("adamw_chunk_elems", &adamw_chunk_elems);

@@ -184,6 +184,25 @@ BF16_F32(void, embedding_bwd, const int64_t* ids, const void* dout, float* ws,
          int64_t N, int64_t H, int64_t vocab_start, int64_t vocab_local,
          int64_t padding_row, hipStream_t stream);
 
+// moe.hip: n tokens, E experts, k choices per token, copy f = i * k + j
+int moe_tokens_per_block(int64_t n);
+// hist / psum_part: [ceil(n / moe_tokens_per_block(n)), E] workspaces
+void moe_route_f32(const float* logits, float* gates, int* idx, int* hist,
+                   float* psum_part, int* counts, int* offsets, float* psum,
+                   int* slot, int* row_of_slot, int n, int E, int k,
+                   hipStream_t stream);
+void moe_route_bwd_f32(const float* logits, const int* idx, const float* gates,
+                       const float* dgates, const float* dpsum, float* dlogits, int n,
+                       int E, int k, hipStream_t stream);
+BF16_F32(void, moe_permute, const void* x, const int* row_of_slot, void* xk, int n,
+         int k, int H, hipStream_t stream);
+// gates == null: unweighted sum (the permute backward); residual may be null
+BF16_F32(void, moe_combine, const void* yk, const float* gates, const int* slot,
+         const void* residual, void* y, int n, int k, int H, hipStream_t stream);
+BF16_F32(void, moe_combine_bwd, const void* dy, const void* yk, const float* gates,
+         const int* row_of_slot, void* dyk, float* dgates, int n, int k, int H,
+         hipStream_t stream);
+
 // gemm_dw.hip
 void gemm_dw_bf16(const void* dy, const void* x, float* ws, void* out,
                   int out_is_bf16, int64_t M, int64_t N, int64_t K, int64_t splits,

@@ -29,6 +29,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 from torch import nn
 
+from ..ops.moe import moe_combine, moe_permute, moe_route
 from ..utils import distributed as du
 
 __all__ = ["MoELayer"]
@@ -63,7 +64,7 @@ class MoELayer(nn.Module):
     def __init__(self, hidden_size, ffn_hidden_size, num_experts, top_k=2,
                  activation="gelu", init_method=nn.init.xavier_normal_,
                  output_layer_init_method=None, aux_loss_coef=0.01,
-                 *, layer_idx=0):
+                 *, layer_idx=0, fused_dispatch=False):
         super().__init__()
         dutil = du.get_dist_util()
         tp = dutil.tensor_parallel_size
@@ -80,6 +81,9 @@ class MoELayer(nn.Module):
         self.aux_loss_coef = aux_loss_coef
         self.layer_idx = layer_idx
         self.last_aux_loss = None
+        # route / permute / combine through the HIP ops of ops/moe.py on CUDA
+        # inputs (plain attribute: tests and A/Bs flip it on a built layer)
+        self.fused_dispatch = fused_dispatch
         output_layer_init_method = output_layer_init_method or init_method
 
         self.router = nn.Linear(hidden_size, num_experts, bias=False)
@@ -110,7 +114,63 @@ class MoELayer(nn.Module):
             else F.silu(h)
         return F.linear(h, self.w2[e], self.b2[e])
 
+    def _forward_fused(self, hidden_states, residual=None):
+        """forward() on the ops of ops/moe.py: same routing, same expert order,
+        one host read of the per-expert counts."""
+        orig_shape = hidden_states.shape
+        x = hidden_states.reshape(-1, self.hidden_size)
+        n = x.shape[0]
+
+        logits = F.linear(x.float(), self.router.weight.float())  # [n, E]
+        gates, idx, counts, psum, plan = moe_route(logits, self.top_k)
+        frac = counts.float() / (n * self.top_k)
+        self.last_aux_loss = self.num_experts * (frac * (psum / n)).sum() \
+            * self.aux_loss_coef
+
+        xk = moe_permute(x, plan)
+        if self.ep > 1 and dist.is_initialized():
+            group = du.get_dist_util().data_parallel_group
+            cpe = counts.long().reshape(self.ep, self.experts_per_rank).contiguous()
+            send = cpe.sum(-1)
+            recv = torch.empty_like(send)
+            dist.all_to_all_single(recv, send, group=group)
+            in_splits = send.tolist()
+            out_splits = recv.tolist()
+            xr = _AllToAll.apply(xk, out_splits, in_splits, group)
+            # receive side: the regroup by local expert stays torch
+            cpe_recv = torch.empty_like(cpe)
+            dist.all_to_all_single(cpe_recv, cpe, group=group)  # [src, le]
+            seg_expert = torch.repeat_interleave(
+                torch.arange(self.experts_per_rank, device=x.device)
+                .repeat(self.ep), cpe_recv.reshape(-1))
+            regroup = torch.argsort(seg_expert, stable=True)
+            xr = xr[regroup]
+            per_expert = cpe_recv.sum(0).tolist()
+        else:
+            xr = xk
+            regroup = None
+            per_expert = counts.tolist()
+
+        outs = []
+        off = 0
+        for e, ne in enumerate(per_expert):
+            outs.append(self._expert_ffn(xr[off : off + ne], e))
+            off += ne
+        yr = torch.cat(outs, dim=0)
+
+        if regroup is not None:
+            inv = torch.empty_like(regroup)
+            inv[regroup] = torch.arange(regroup.numel(), device=x.device)
+            yk = _AllToAll.apply(yr[inv], in_splits, out_splits, group)
+        else:
+            yk = yr
+
+        res = None if residual is None else residual.reshape(n, self.hidden_size)
+        return moe_combine(yk, gates, plan, res).reshape(orig_shape)
+
     def forward(self, hidden_states, residual=None):
+        if self.fused_dispatch and hidden_states.is_cuda:
+            return self._forward_fused(hidden_states, residual)
         orig_shape = hidden_states.shape
         x = hidden_states.reshape(-1, self.hidden_size)
         n = x.shape[0]

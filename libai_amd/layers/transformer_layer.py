@@ -45,6 +45,7 @@ class TransformerLayer(nn.Module):
         fuse_residual_norm=True,
         flash_prefill=False,
         flash_cross_attention=False,
+        moe_fused_dispatch=False,
     ):
         super().__init__()
         self.layer_idx = layer_idx
@@ -103,6 +104,7 @@ class TransformerLayer(nn.Module):
                 init_method=init_method,
                 output_layer_init_method=output_layer_init_method,
                 layer_idx=layer_idx,
+                fused_dispatch=moe_fused_dispatch,
             )
         elif mlp_type == "gated":
             from .mlp import GatedMLP

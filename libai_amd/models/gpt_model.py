@@ -66,7 +66,7 @@ class Transformer(nn.Module):
                  bias_dropout_fusion, scale_mask_softmax_fusion,
                  apply_query_key_layer_scaling, apply_residual_post_layernorm,
                  sequence_parallel=False, moe_num_experts=0, moe_top_k=2,
-                 flash_prefill=False):
+                 flash_prefill=False, moe_fused_dispatch=False):
         super().__init__()
         self.num_layers = num_layers
         self.checkpoint_activations = False
@@ -91,6 +91,7 @@ class Transformer(nn.Module):
                     moe_top_k=moe_top_k,
                     layer_idx=i,
                     flash_prefill=flash_prefill,
+                    moe_fused_dispatch=moe_fused_dispatch,
                 )
                 for i in range(num_layers)
             ]
@@ -148,6 +149,7 @@ class GPTModel(nn.Module):
         moe_top_k=2,
         amp_enabled=False,
         flash_prefill=False,
+        moe_fused_dispatch=False,
     ):
         super().__init__()
         self.sequence_parallel = sequence_parallel
@@ -172,6 +174,7 @@ class GPTModel(nn.Module):
             sequence_parallel=sequence_parallel,
             moe_num_experts=moe_num_experts, moe_top_k=moe_top_k,
             flash_prefill=flash_prefill,
+            moe_fused_dispatch=moe_fused_dispatch,
         )
         self.lm_head = LMLogits(vocab_size, bias=False,
                                 sequence_parallel=sequence_parallel, layer_idx=-1)
@@ -211,6 +214,7 @@ class GPTModel(nn.Module):
             "moe_top_k": cfg.get("moe_top_k", 2),
             "amp_enabled": cfg.get("amp_enabled", False),
             "flash_prefill": cfg.get("flash_prefill", False),
+            "moe_fused_dispatch": cfg.get("moe_fused_dispatch", False),
         }
 
     def forward(self, input_ids, past_key_values=None, use_cache=False,

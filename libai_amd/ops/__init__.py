@@ -7,6 +7,7 @@ from .attention import (
 )
 from .cross_entropy import vocab_parallel_cross_entropy
 from .fused_bias import bias_dropout_add, bias_gelu
+from .moe import moe_combine, moe_fused_available, moe_permute, moe_route
 from .norm import (
     bias_dropout_add_norm,
     layer_norm,
@@ -37,4 +38,8 @@ __all__ = [
     "apply_rotary_pos_emb",
     "RotaryEmbedding",
     "swiglu",
+    "moe_route",
+    "moe_permute",
+    "moe_combine",
+    "moe_fused_available",
 ]
