@@ -4,33 +4,32 @@ Explicit re-design of the reference MultiheadAttention
 (reference: libai/layers/attention.py:88-281):
 
   * fused QKV column-parallel linear (hidden -> 3*hidden/tp, attention.py:118-124)
-  * batched QK^T and PV through rocBLAS (torch.matmul), scores shaped
-    [b, nh/tp, s, s]
-  * fused scale+causal/padding softmax(+dropout) HIP kernel (replaces
-    flow._C.fused_scale_tril_softmax_mask_scale / fused_scale_mask_softmax_dropout,
-    attention.py:221-246)
   * row-parallel output projection; its bias/dropout/residual-add is fused by
     the caller (TransformerLayer) via bias_dropout_add, matching the
     reference's fused_bias_add_dropout site (attention.py:265-267)
   * KV-cache incremental decoding (attention.py:201-208) and the
     cross-attention Q + KV split (attention.py:102-116).
-  * opt-in flash routes, both off by default: ``flash_prefill`` sends the
-    cached inference passes of a causal self-attention (prompt pass with
-    ``use_cache``, multi-token step on a past) through the flash forward with
-    the past length as the query offset (``"split"``: also the short chunks
-    on long caches that ``True`` leaves to the materialized route, through
-    the split-KV forward); ``flash_cross_attention`` sends the
-    no-cache cross-attention call through the flash forward/backward on the
-    packed key/value projection.
+
+``forward`` asks ``_route`` which kernel serves the call, runs that route's
+method and hands its context to one shared tail.  docs/architecture.md,
+"Attention routes", lists every route with its conditions and its op.
 """
 
 import math
+from types import SimpleNamespace
 
 import torch
 from torch import nn
 
+# the names of ops.attention are looked up through the module at call time
+from ..ops import attention as attn_ops
+from ..ops._ext import ext
 from ..ops.fused_bias import bias_dropout_add
 from ..ops.softmax import fused_scale_mask_softmax
+from ..utils import distributed as du
+from .linear import Linear1D
+
+__all__ = ["MultiheadAttention", "AttnMaskType"]
 
 _DUMMY_TABS = {}
 
@@ -53,10 +52,6 @@ def _rel_table_fits(table, num_heads, s, device):
         and table.device == device
         and tuple(table.shape) == (num_heads, 2 * s - 1)
     )
-from ..utils import distributed as du
-from .linear import Linear1D
-
-__all__ = ["MultiheadAttention", "AttnMaskType"]
 
 
 class AttnMaskType:
@@ -115,6 +110,11 @@ class MultiheadAttention(nn.Module):
         if apply_query_key_layer_scaling:
             self.coeff = float(layer_idx + 1)
             self.norm_factor /= self.coeff
+        # the reference's query_key_layer_scaling splits the scale between the
+        # matmul alpha and the softmax input (attention.py:211, :240); in bf16 we
+        # fold the whole 1/sqrt(hs) (incl. coeff round-trip = identity) into the
+        # one scale every kernel takes.
+        self.softmax_scale = self.norm_factor * (self.coeff if self.coeff else 1.0)
 
         output_layer_init_method = output_layer_init_method or init_method
         if is_cross_attention:
@@ -133,11 +133,91 @@ class MultiheadAttention(nn.Module):
                               sequence_parallel=sequence_parallel,
                               layer_idx=layer_idx)
 
-    def _split_heads(self, x, n):
-        # [b, s, n*hs] -> [b, nh_local, s, hs] per chunk
-        b, s, _ = x.shape
-        x = x.view(b, s, self.num_heads_local, n * self.head_size)
-        return x.permute(0, 2, 1, 3).chunk(n, dim=-1)
+    def _route(self, b, sq, sk, dtype, device, attention_mask=None,
+               position_bias=None, has_past=False, use_cache=False,
+               static_cache=False):
+        """The name of the route that serves a call of ``b`` sequences with
+        ``sq`` queries on ``sk`` keys (for a step on a cache: the past length
+        plus ``sq``).  Decided from the module's flags, the training and grad
+        modes and what the mask and the bias carry, before anything is
+        projected; plain values in, so it runs without a GPU."""
+        if static_cache:
+            return "static_decode"
+        hs = self.head_size
+        cached = has_past or use_cache
+        if self.is_cross_attention:
+            if (
+                self.flash_cross_attention
+                and not cached
+                and position_bias is None
+                and attn_ops.flash_cross_available(hs, dtype, device, sq, sk,
+                                                   attention_mask)
+            ):
+                return "flash_cross"
+            return "materialized"
+
+        # an ALiBi bias from build_alibi_bias carries its fp32 slopes: the
+        # fused kernels add slope * (kv - q) in-register and never read the
+        # tensor.  A T5 relative-position bias carries its fp32 diagonal table:
+        # the flash kernels add table[h, kv - q + s - 1] and return the table
+        # gradient (training / no-cache path only; the decode kernels take no
+        # table).  Any other bias (Swin, user-supplied, a sliced T5 bias) has
+        # neither attribute and takes the materialized route.
+        slopes = attn_ops.bias_alibi_slopes(position_bias)
+        bias_fusable = position_bias is None or slopes is not None
+        if not cached:
+            rel_table = attn_ops.bias_rel_table(position_bias) if slopes is None else None
+            if (
+                (bias_fusable or rel_table is not None)
+                and attn_ops.flash_attention_available(hs, dtype, device, sq, sq,
+                                                       attention_mask)
+                and (rel_table is None or _rel_table_fits(
+                    rel_table, self.num_heads_local, sq, device))
+            ):
+                return "flash_qkv"
+            return "materialized"
+
+        # flash_prefill: the cached passes of a causal self-attention, in
+        # inference, with no mask but a right-padding one and no bias but ALiBi
+        prefill = (
+            self.flash_prefill
+            and not self.training
+            and self.attn_mask_type == AttnMaskType.causal
+            and bias_fusable
+            and (attention_mask is None
+                 or attn_ops.mask_kv_len(attention_mask) is not None)
+        )
+        if not has_past:
+            # prompt pass of any length (the key count may be ragged)
+            if prefill and attn_ops.flash_prefill_available(hs, dtype, device, sq, sq):
+                return "flash_prompt"
+            return "materialized"
+        if prefill:
+            chunk = attn_ops.flash_chunk_route(
+                self.flash_prefill, hs, dtype, device, b, self.num_heads_local, 1,
+                sq, sk)
+            if chunk is not None:
+                return "flash_chunk_split" if chunk == "split" else "flash_chunk"
+        # what decode_attention_available reads of the query, before it exists
+        query = SimpleNamespace(device=device, dtype=dtype, shape=(sq, hs))
+        if (
+            attention_mask is None
+            and bias_fusable
+            and attn_ops.decode_attention_available(query, hs)
+        ):
+            return "decode"
+        return "materialized"
+
+    def _call_shape(self, hidden_states, encoder_states, past_key_value):
+        """(b, sq, sk) of a call: sk counts the past of a self-attention step."""
+        b, sq, _ = hidden_states.shape
+        if self.sequence_parallel:  # input is the seq shard; qkv gathers
+            sq = sq * du.get_dist_util().tensor_parallel_size
+        past_len = past_key_value[0].shape[2] if past_key_value is not None else 0
+        if self.is_cross_attention:
+            return b, sq, past_len if past_key_value is not None \
+                else encoder_states.shape[1]
+        return b, sq, sq + past_len
 
     def forward(
         self,
@@ -167,168 +247,132 @@ class MultiheadAttention(nn.Module):
         bias + dropout + residual fused with the norm that follows.
         """
         assert not raw_output or (past_key_value is None and not use_cache)
-        if static_cache is not None:
-            # hipGraph-capturable decode: preallocated [b, nh, MAX, hs] caches,
-            # device position/length tensors; ONE kv_insert kernel (no-rotate
-            # variant of K17's decode fusion) moves q to flash layout and
-            # writes k/v into the cache row at the device position; fused
-            # flash_decode masks by per-batch kv_len (all shapes static)
-            from ..ops._ext import ext
-            from ..ops.attention import flash_decode_attn
+        b, sq, sk = self._call_shape(hidden_states, encoder_states, past_key_value)
+        route = self._route(
+            b, sq, sk, hidden_states.dtype, hidden_states.device, attention_mask,
+            position_bias, past_key_value is not None, use_cache,
+            static_cache is not None)
 
-            ck, cv, kv_len32 = static_cache
-            qkv = self.query_key_value(hidden_states)
-            b, s, _ = hidden_states.shape
-            nh, hs = self.num_heads_local, self.head_size
-            qkv4 = qkv.view(b, s, nh, 3 * hs)
-            q, k, v = (qkv4[..., :hs], qkv4[..., hs:2 * hs], qkv4[..., 2 * hs:])
-            dummy = _dummy_tab(hidden_states.device)
-            qo = ext().rope_kv_insert(q, k, v, ck, cv, dummy, dummy,
-                                      position, False)
-            scale_c = self.norm_factor * (self.coeff if self.coeff else 1.0)
-            ctx = flash_decode_attn(qo, ck, cv, scale_c, kv_len=kv_len32)
-            context = ctx.permute(0, 2, 1, 3).reshape(b, 1, nh * hs)
+        if route == "static_decode":
+            context, present = self._static_decode(hidden_states, static_cache, position)
             # returns RAW (out, bias): the layer fuses bias+residual+norm
-            return self.dense(context)
+            raw_output = True
+        elif route == "flash_qkv":
+            context, present = self._flash_qkv(hidden_states, attention_mask,
+                                               position_bias)
+        elif route == "flash_cross":
+            context, present = self._flash_cross(hidden_states, encoder_states,
+                                                 attention_mask)
+        elif route == "flash_prompt":
+            context, present = self._flash_prompt(hidden_states, attention_mask,
+                                                  position_bias)
+        elif route in ("flash_chunk", "flash_chunk_split"):
+            # a few workgroups on a long cache: flash_prefill="split" sends the
+            # chunk to the split-KV forward where its policy accepts the shape
+            context, present = self._flash_chunk(
+                hidden_states, attention_mask, past_key_value, position_bias,
+                kv_split="auto" if route == "flash_chunk_split" else None)
+        elif route == "decode":
+            context, present = self._decode(hidden_states, past_key_value,
+                                            position_bias)
+        else:
+            context, present = self._materialized(
+                hidden_states, encoder_states, attention_mask, past_key_value,
+                position_bias)
 
-        # an ALiBi bias from build_alibi_bias carries its fp32 slopes: the
-        # fused kernels add slope * (kv - q) in-register and never read the
-        # tensor.  A T5 relative-position bias carries its fp32 diagonal table:
-        # the flash kernels add table[h, kv - q + s - 1] and return the table
-        # gradient (training / no-cache path only; the decode kernels take no
-        # table).  Any other bias (Swin, user-supplied, a sliced T5 bias) has
-        # neither attribute and takes the materialized path below.
-        from ..ops.attention import (
-            bias_alibi_slopes,
-            bias_rel_table,
-            flash_chunk_pays,
-            flash_prefill_available,
-            flash_split_keys,
-            mask_kv_len,
+        out, bias = self.dense(context)
+        if raw_output:
+            return out, bias
+        out = bias_dropout_add(
+            out, bias=bias, residual=residual, p=self.output_dropout_prob,
+            training=self.training,
         )
+        return (out, present) if use_cache else out
 
-        slopes = bias_alibi_slopes(position_bias)
-        bias_fusable = position_bias is None or slopes is not None
-        rel_table = bias_rel_table(position_bias) if slopes is None else None
+    # -- routes: each projects, calls its op and returns (context, present) --
 
+    def _static_decode(self, hidden_states, static_cache, position):
+        # hipGraph-capturable decode: preallocated [b, nh, MAX, hs] caches,
+        # device position/length tensors; ONE kv_insert kernel (no-rotate
+        # variant of K17's decode fusion) moves q to flash layout and
+        # writes k/v into the cache row at the device position; fused
+        # flash_decode masks by per-batch kv_len (all shapes static)
+        ck, cv, kv_len32 = static_cache
+        qkv = self.query_key_value(hidden_states)
+        b, s, _ = hidden_states.shape
+        nh, hs = self.num_heads_local, self.head_size
+        qkv4 = qkv.view(b, s, nh, 3 * hs)
+        q, k, v = (qkv4[..., :hs], qkv4[..., hs:2 * hs], qkv4[..., 2 * hs:])
+        dummy = _dummy_tab(hidden_states.device)
+        qo = ext().rope_kv_insert(q, k, v, ck, cv, dummy, dummy, position, False)
+        ctx = attn_ops.flash_decode_attn(qo, ck, cv, self.softmax_scale,
+                                         kv_len=kv_len32)
+        return ctx.permute(0, 2, 1, 3).reshape(b, 1, nh * hs), None
+
+    def _packed_qkv(self, hidden_states):
+        """The fused projection as [b, s, nh, 3, hs]: a view, ZERO copies."""
+        qkv = self.query_key_value(hidden_states)
+        b, s, _ = qkv.shape
+        return qkv.view(b, s, self.num_heads_local, 3, self.head_size)
+
+    def _flash_qkv(self, hidden_states, attention_mask, position_bias):
         # fused flash path: consumes the qkv buffer with ZERO copies (strided
         # [b, s, nh, hs] views), O lands directly in [b, s, h] layout.
-        if (
-            not self.is_cross_attention
-            and past_key_value is None
-            and not use_cache
-            and (bias_fusable or rel_table is not None)
-        ):
-            from ..ops.attention import (
-                flash_attention_available,
-                flash_attention_qkv,
-                mask_kv_len,
-            )
+        qkv5 = self._packed_qkv(hidden_states)
+        slopes = attn_ops.bias_alibi_slopes(position_bias)
+        o = attn_ops.flash_attention_qkv(
+            qkv5,
+            scale=self.softmax_scale,
+            p_drop=self.attention_dropout_prob,
+            causal=self.attn_mask_type == AttnMaskType.causal,
+            training=self.training,
+            kv_len=attn_ops.mask_kv_len(attention_mask),
+            alibi_slopes=slopes,
+            rel_bias=attn_ops.bias_rel_table(position_bias) if slopes is None else None,
+        )
+        return o.reshape(o.shape[0], o.shape[1], -1), None
 
-            b, s, _ = hidden_states.shape
-            if self.sequence_parallel:  # input is the seq shard; qkv gathers
-                s = s * du.get_dist_util().tensor_parallel_size
-            if flash_attention_available(
-                self.head_size, hidden_states.dtype, hidden_states.device, s, s,
-                attention_mask,
-            ) and (rel_table is None or _rel_table_fits(
-                rel_table, self.num_heads_local, s, hidden_states.device
-            )):
-                qkv = self.query_key_value(hidden_states)
-                qkv5 = qkv.view(b, s, self.num_heads_local, 3, self.head_size)
-                o = flash_attention_qkv(
-                    qkv5,
-                    scale=self.norm_factor * (self.coeff if self.coeff else 1.0),
-                    p_drop=self.attention_dropout_prob,
-                    causal=self.attn_mask_type == AttnMaskType.causal,
-                    training=self.training,
-                    kv_len=mask_kv_len(attention_mask),
-                    alibi_slopes=slopes,
-                    rel_bias=rel_table,
-                )
-                context = o.reshape(b, s, self.num_heads_local * self.head_size)
-                out, bias = self.dense(context)
-                if raw_output:
-                    return out, bias
-                return bias_dropout_add(
-                    out, bias=bias, residual=residual, p=self.output_dropout_prob,
-                    training=self.training,
-                )
+    def _flash_cross(self, hidden_states, encoder_states, attention_mask):
+        # both projections consumed as they come, zero copies: q as
+        # [b, sq, nh, hs], key_value as packed [b, sk, nh, 2, hs]
+        b, sq, _ = hidden_states.shape
+        sk = encoder_states.shape[1]
+        nh, hs = self.num_heads_local, self.head_size
+        q4 = self.query(hidden_states).view(b, sq, nh, hs)
+        kv5 = self.key_value(encoder_states).view(b, sk, nh, 2, hs)
+        o = attn_ops.flash_attention_kv(
+            q4, kv5,
+            scale=self.softmax_scale,
+            p_drop=self.attention_dropout_prob,
+            training=self.training,
+            kv_len=attn_ops.mask_kv_len(attention_mask),
+        )
+        return o.reshape(b, sq, nh * hs), None
 
-        if (
-            self.is_cross_attention
-            and self.flash_cross_attention
-            and past_key_value is None
-            and not use_cache
-            and position_bias is None
-        ):
-            from ..ops.attention import flash_attention_kv, flash_cross_available
+    def _flash_prompt(self, hidden_states, attention_mask, position_bias):
+        qkv5 = self._packed_qkv(hidden_states)
+        o = attn_ops.flash_attention_qkv(
+            qkv5,
+            scale=self.softmax_scale,
+            causal=True,
+            training=False,
+            kv_len=attn_ops.mask_kv_len(attention_mask),
+            alibi_slopes=attn_ops.bias_alibi_slopes(position_bias),
+        )
+        # the cache layout, [b, nh, s, hs]: the views _split_heads gives
+        present = (qkv5[..., 1, :].permute(0, 2, 1, 3),
+                   qkv5[..., 2, :].permute(0, 2, 1, 3))
+        return o.reshape(o.shape[0], o.shape[1], -1), present
 
-            b, sq, _ = hidden_states.shape
-            sk = encoder_states.shape[1]
-            if flash_cross_available(
-                self.head_size, hidden_states.dtype, hidden_states.device, sq, sk,
-                attention_mask,
-            ):
-                # both projections consumed as they come, zero copies: q as
-                # [b, sq, nh, hs], key_value as packed [b, sk, nh, 2, hs]
-                nh, hs = self.num_heads_local, self.head_size
-                q4 = self.query(hidden_states).view(b, sq, nh, hs)
-                kv5 = self.key_value(encoder_states).view(b, sk, nh, 2, hs)
-                o = flash_attention_kv(
-                    q4, kv5,
-                    scale=self.norm_factor * (self.coeff if self.coeff else 1.0),
-                    p_drop=self.attention_dropout_prob,
-                    training=self.training,
-                    kv_len=mask_kv_len(attention_mask),
-                )
-                out, bias = self.dense(o.reshape(b, sq, nh * hs))
-                if raw_output:
-                    return out, bias
-                return bias_dropout_add(
-                    out, bias=bias, residual=residual, p=self.output_dropout_prob,
-                    training=self.training,
-                )
+    def _split_heads(self, x, n):
+        # [b, s, n*hs] -> [b, nh_local, s, hs] per chunk
+        b, s, _ = x.shape
+        x = x.view(b, s, self.num_heads_local, n * self.head_size)
+        return x.permute(0, 2, 1, 3).chunk(n, dim=-1)
 
-        # flash_prefill: the cached passes of a causal self-attention, in
-        # inference, with no mask but a right-padding one and no bias but ALiBi
-        prefill = False
-        if (
-            self.flash_prefill
-            and not self.is_cross_attention
-            and not self.training
-            and self.attn_mask_type == AttnMaskType.causal
-            and bias_fusable
-        ):
-            prefill = attention_mask is None or mask_kv_len(attention_mask) is not None
-        if prefill and use_cache and past_key_value is None:
-            from ..ops.attention import flash_attention_qkv
-
-            b, s, _ = hidden_states.shape
-            if flash_prefill_available(self.head_size, hidden_states.dtype,
-                                       hidden_states.device, s, s):
-                # prompt pass of any length (the key count may be ragged)
-                qkv = self.query_key_value(hidden_states)
-                qkv5 = qkv.view(b, s, self.num_heads_local, 3, self.head_size)
-                o = flash_attention_qkv(
-                    qkv5,
-                    scale=self.norm_factor * (self.coeff if self.coeff else 1.0),
-                    causal=True,
-                    training=False,
-                    kv_len=mask_kv_len(attention_mask),
-                    alibi_slopes=slopes,
-                )
-                # the cache layout, [b, nh, s, hs]: the views _split_heads gives
-                present = (qkv5[..., 1, :].permute(0, 2, 1, 3),
-                           qkv5[..., 2, :].permute(0, 2, 1, 3))
-                out, bias = self.dense(
-                    o.reshape(b, s, self.num_heads_local * self.head_size))
-                out = bias_dropout_add(
-                    out, bias=bias, residual=residual, p=self.output_dropout_prob,
-                    training=self.training,
-                )
-                return out, present
-
+    def _project_heads(self, hidden_states, encoder_states, past_key_value):
+        """q, k, v as [b, nh, s, hs], the past in front of the new keys (for a
+        cross-attention the past IS the keys)."""
         if self.is_cross_attention:
             q = self._split_heads(self.query(hidden_states), 1)[0]
             if past_key_value is not None:
@@ -341,104 +385,61 @@ class MultiheadAttention(nn.Module):
                 pk, pv = past_key_value
                 k = torch.cat([pk, k], dim=2)
                 v = torch.cat([pv, v], dim=2)
-        present = (k, v) if use_cache else None
+        return q, k, v
 
-        scale_d = self.norm_factor * (self.coeff if self.coeff else 1.0)
-        chunk = (
-            prefill
-            and past_key_value is not None
-            and q.shape[2] > 1
-            and flash_prefill_available(self.head_size, q.dtype, q.device,
-                                        q.shape[2], k.shape[2])
+    def _flash_chunk(self, hidden_states, attention_mask, past_key_value,
+                     position_bias, kv_split):
+        q, k, v = self._project_heads(hidden_states, None, past_key_value)
+        # a chunk behind the cache: query i sits at key past_len + i; the
+        # kernel takes the head-major tensors through [b, s, nh, hs] views
+        o = attn_ops.flash_attention(
+            q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3),
+            self.softmax_scale, causal=True, training=False,
+            kv_len=attn_ops.mask_kv_len(attention_mask),
+            alibi_slopes=attn_ops.bias_alibi_slopes(position_bias),
+            q_offset=past_key_value[0].shape[2], kv_split=kv_split,
         )
-        # a few workgroups on a long cache: flash_prefill="split" sends the
-        # chunk to the split-KV forward where its policy accepts the shape
-        kv_split = None
-        if chunk and not flash_chunk_pays(q.shape[0], q.shape[1], q.shape[2],
-                                          k.shape[2]):
-            chunk = self.flash_prefill == "split" and flash_split_keys(
-                q.shape[0], k.shape[1], q.shape[1] // k.shape[1], q.shape[2],
-                k.shape[2]) > 0
-            kv_split = "auto"
-        if chunk:
-            from ..ops.attention import flash_attention
+        b, sq, nh, hs = o.shape
+        return o.reshape(b, sq, nh * hs), (k, v)
 
-            # a chunk behind the cache: query i sits at key past_len + i; the
-            # kernel takes the head-major tensors through [b, s, nh, hs] views
-            o = flash_attention(
-                q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3),
-                scale_d, causal=True, training=False,
-                kv_len=mask_kv_len(attention_mask), alibi_slopes=slopes,
-                q_offset=past_key_value[0].shape[2], kv_split=kv_split,
-            )
-            b, sq, nh, hs = o.shape
-            out, bias = self.dense(o.reshape(b, sq, nh * hs))
-            out = bias_dropout_add(
-                out, bias=bias, residual=residual, p=self.output_dropout_prob,
-                training=self.training,
-            )
-            return (out, present) if use_cache else out
-        if (
-            past_key_value is not None
-            and attention_mask is None
-            and bias_fusable
-            and not self.is_cross_attention
-        ):
-            from ..ops.attention import (
-                decode_attention_available,
-                flash_decode_attn,
-            )
+    def _decode(self, hidden_states, past_key_value, position_bias):
+        q, k, v = self._project_heads(hidden_states, None, past_key_value)
+        # fused single-token decode (K16): no [b, nh, 1, skv] scores
+        # (ALiBi: the new token is the last key, so key index ==
+        # absolute position and the kernel's qpos = skv - 1)
+        ctx = attn_ops.flash_decode_attn(
+            q.contiguous(), k, v, self.softmax_scale,
+            alibi_slopes=attn_ops.bias_alibi_slopes(position_bias))
+        b, nh, _, hs = ctx.shape
+        return ctx.permute(0, 2, 1, 3).reshape(b, 1, nh * hs), (k, v)
 
-            if decode_attention_available(q, self.head_size):
-                # fused single-token decode (K16): no [b, nh, 1, skv] scores
-                # (ALiBi: the new token is the last key, so key index ==
-                # absolute position and the kernel's qpos = skv - 1)
-                ctx = flash_decode_attn(q.contiguous(), k, v, scale_d,
-                                        alibi_slopes=slopes)
-                b, nh, _, hs = ctx.shape
-                context = ctx.permute(0, 2, 1, 3).reshape(b, 1, nh * hs)
-                out, bias = self.dense(context)
-                out = bias_dropout_add(
-                    out, bias=bias, residual=residual,
-                    p=self.output_dropout_prob, training=self.training,
-                )
-                return (out, present) if use_cache else out
-
+    def _materialized(self, hidden_states, encoder_states, attention_mask,
+                      past_key_value, position_bias):
+        # batched QK^T and PV through rocBLAS, fused scale + causal/padding
+        # softmax (+ dropout) kernel in between (replaces
+        # flow._C.fused_scale_tril_softmax_mask_scale /
+        # fused_scale_mask_softmax_dropout, attention.py:221-246)
+        q, k, v = self._project_heads(hidden_states, encoder_states, past_key_value)
         # [b, nh, sq, hs] x [b, nh, hs, sk] -> [b, nh, sq, sk]  (rocBLAS bmm)
         scores = torch.matmul(q, k.transpose(-1, -2))
-        # the reference's query_key_layer_scaling splits the scale between the
-        # matmul alpha and the softmax input (attention.py:211, :240); in bf16 we
-        # fold the whole 1/sqrt(hs) (incl. coeff round-trip = identity) into the
-        # fused softmax's scale argument.
-        scale = self.norm_factor * (self.coeff if self.coeff else 1.0)
+        scale = self.softmax_scale
         if position_bias is not None:
             # additive score bias (ALiBi / T5 relative positions): fold the
             # scale here so the fused softmax runs with scale=1
             scores = scores * scale + position_bias
             scale = 1.0
-        causal = self.attn_mask_type == AttnMaskType.causal and past_key_value is None
         probs = fused_scale_mask_softmax(
             scores,
             pad_mask=attention_mask,
             scale=scale,
             p=self.attention_dropout_prob,
-            causal=causal,
+            # a step on a past sees every cached key
+            causal=self.attn_mask_type == AttnMaskType.causal and past_key_value is None,
             training=self.training,
         )
         context = torch.matmul(probs, v)  # [b, nh, sq, hs]
         b, nh, sq, hs = context.shape
-        context = context.permute(0, 2, 1, 3).reshape(b, sq, nh * hs)
-
-        out, bias = self.dense(context)
-        if raw_output:
-            return out, bias
-        out = bias_dropout_add(
-            out, bias=bias, residual=residual, p=self.output_dropout_prob,
-            training=self.training,
-        )
-        if use_cache:
-            return out, present
-        return out
+        return context.permute(0, 2, 1, 3).reshape(b, sq, nh * hs), (k, v)
 
     def extra_repr(self):
         return (

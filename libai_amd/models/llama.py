@@ -6,6 +6,7 @@ vocab-parallel output head + vocab-parallel CE.
 """
 
 import math
+from types import SimpleNamespace
 
 import torch
 from torch import nn
@@ -13,14 +14,17 @@ from torch.utils.checkpoint import checkpoint as act_checkpoint
 
 from ..config import configurable
 from ..layers import Linear1D, LMLogits, ParallelCrossEntropyLoss, RMSLayerNorm, VocabEmbedding
+# the decode and chunk-policy names are looked up on ops.attention at call
+# time, so a substitute set there is seen here; flash_attention_available is
+# a global of this module, where callers substitute it
+from ..ops import attention as attn_ops
+from ..ops._ext import ext
 from ..ops.attention import (
     flash_attention,
     flash_attention_available,
-    flash_chunk_pays,
     flash_prefill_available,
-    flash_split_keys,
 )
-from ..ops.rope import apply_rotary_pos_emb
+from ..ops.rope import _tables, apply_rotary_pos_emb
 from ..ops.softmax import fused_scale_mask_softmax
 from ..ops.swiglu import swiglu
 from ..utils import distributed as du
@@ -39,13 +43,16 @@ class LlamaAttention(nn.Module):
 
     sliding_window=W (Mistral): causal attention over the last W keys, the
     query's own included (HF's ``q_idx - kv_idx < sliding_window``); every
-    branch of forward honours it.  The KV cache keeps all keys.
+    route honours it.  The KV cache keeps all keys.
 
     doc_start / doc_end (int32 [b, s], ``libai_amd.data.packing``): packed
     documents.  Attention stays causal inside each token's own document and
     RoPE runs on ``position_ids`` that restart at every document; the flash
-    branch masks in-kernel, the unfused branch builds the same mask.  Training
-    and scoring only: no KV cache, no sliding window."""
+    route masks in-kernel, the unfused route builds the same mask.  Training
+    and scoring only: no KV cache, no sliding window.
+
+    ``forward`` asks ``_route`` which kernel serves the call and runs that
+    route's method (docs/architecture.md, "Attention routes")."""
 
     def __init__(self, hidden_size, num_heads, max_position_embeddings,
                  init_method, output_init_method, rope_theta=10000.0,
@@ -126,161 +133,163 @@ class LlamaAttention(nn.Module):
             doc_end = doc_end.to(torch.int32).contiguous()
             if position_ids is None:  # called without LlamaModel
                 position_ids = _doc_position_ids(doc_start)
-        if static_cache is not None:
-            # hipGraph-capturable decode: RoPE at a device position tensor,
-            # in-place KV insert into [b, kvh, MAX, hd] buffers, fused
-            # flash_decode masked by device int32 kv_len (GQA in-kernel)
-            from ..ops._ext import ext
-            from ..ops.attention import flash_decode_attn
-            from ..ops.rope import _tables
-
-            ck, cv, kv32 = static_cache
-            b, _, _ = hidden_states.shape
-            q, k, v = self._project(hidden_states)
-            # ONE kernel: RoPE(q) -> flash layout, RoPE(k)/copy(v) -> cache
-            # row at the device position (replaces ~15 eager-shaped launches)
-            cos_t, sin_t = _tables(self.max_pos, self.head_dim,
-                                   self.rope_theta, hidden_states.device)
-            qo = ext().rope_kv_insert(q, k, v, ck, cv, cos_t, sin_t, position, True)
-            ctx = flash_decode_attn(qo, ck, cv, self.scale, kv_len=kv32,
-                                    window=self.sliding_window)
-            context = ctx.permute(0, 2, 1, 3).reshape(
-                b, 1, self.num_heads_local * self.head_dim)
-            out, _ = self.o_proj(context)
-            return out  # RAW: the layer fuses residual + RMSNorm
-        if self.sequence_parallel and (use_cache or past_key_value is not None):
+        has_past = past_key_value is not None
+        if self.sequence_parallel and static_cache is None and (use_cache or has_past):
             raise RuntimeError("sequence_parallel is training-only; build the "
                                "generation model with sequence_parallel=False")
         b, s, _ = hidden_states.shape
-        if self.sequence_parallel:
+        if self.sequence_parallel:  # col projections gather the seq shards
             s = s * du.get_dist_util().tensor_parallel_size
+        pos0 = past_key_value[0].shape[2] if has_past else 0
+        route = self._route(b, s, pos0 + s, hidden_states.dtype, hidden_states.device,
+                            has_past, use_cache, static_cache is not None)
+
+        if route == "static_decode":
+            context = self._static_decode(hidden_states, static_cache, position)
+            # RAW: the layer fuses residual + RMSNorm
+            return self._output(context, None, None, False)
         q, k, v = self._project(hidden_states)
-        pos0 = past_key_value[0].shape[2] if past_key_value is not None else 0
         q = apply_rotary_pos_emb(q, self.max_pos, self.rope_theta, pos0, position_ids)
         k = apply_rotary_pos_emb(k, self.max_pos, self.rope_theta, pos0, position_ids)
-
-        window = self.sliding_window
-        if (
-            self.flash_prefill
-            and use_cache
-            and past_key_value is None
-            and flash_prefill_available(self.head_dim, q.dtype, q.device, s, s)
-        ):
-            # prompt pass of any length (the key count may be ragged): no
-            # [b, nh, s, s] scores, no repeat_interleave of K and V; the cache
-            # gets every key, in [b, kvh, s, hd]
-            o = flash_attention(q, k, v, self.scale, p_drop=0.0, causal=True,
-                                training=False, window=window)
-            context = o.reshape(b, s, self.num_heads_local * self.head_dim)
-            present = (k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3))
-            out, _ = self.o_proj(context)
-            out = out + residual if residual is not None else out
-            return out, present
-        if (
-            past_key_value is None
-            # a windowed model also runs its prompt pass (use_cache) here, so
-            # a long prefill never materializes S x S scores
-            and (not use_cache or window is not None)
-            and flash_attention_available(self.head_dim, q.dtype, q.device, s, s, None)
-        ):
+        if route in ("flash_prompt", "flash"):
             doc_bounds = (doc_start, doc_end) if doc_start is not None else None
-            o = flash_attention(q, k, v, self.scale, p_drop=0.0, causal=True,
-                                training=self.training, window=window,
-                                doc_bounds=doc_bounds)
-            context = o.reshape(b, s, self.num_heads_local * self.head_dim)
+            context = self._flash(q, k, v, doc_bounds,
+                                  training=route == "flash" and self.training)
+            present = None
             if use_cache:  # the cache gets every key, in [b, kvh, s, hd]
                 present = (k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3))
-                out, _ = self.o_proj(context)
-                out = out + residual if residual is not None else out
-                return out, present
         else:
-            # unfused path (decode / CPU): [b, nh, s, hs]
-            group = self.num_heads_local // self.num_kv_local
+            # the cached steps and the unfused route work head-major,
+            # [b, nh, s, hd], the past in front of the new keys
             qh = q.permute(0, 2, 1, 3)
             kh = k.permute(0, 2, 1, 3)
             vh = v.permute(0, 2, 1, 3)
-            if past_key_value is not None:
+            if has_past:
                 pk, pv = past_key_value
                 kh = torch.cat([pk, kh], dim=2)
                 vh = torch.cat([pv, vh], dim=2)
-            present = (kh, vh) if use_cache else None  # cache holds KV heads
-            from ..ops.attention import (
-                decode_attention_available,
-                flash_decode_attn,
-            )
+            present = (kh, vh)  # cache holds KV heads
+            if route == "decode":
+                context = self._decode(qh, kh, vh)
+            elif route in ("flash_chunk", "flash_chunk_split"):
+                # a few workgroups on a long cache: flash_prefill="split" sends
+                # the chunk to the split-KV forward where its policy accepts it
+                context = self._flash_chunk(
+                    q, kh, vh, q_offset=pos0,
+                    kv_split="auto" if route == "flash_chunk_split" else None)
+            else:
+                context = self._unfused(qh, kh, vh, pos0, doc_start,
+                                        causal=not has_past)
+        return self._output(context, present, residual, use_cache)
 
-            if past_key_value is not None and decode_attention_available(
-                qh, self.head_dim
-            ):
-                # fused single-token decode (K16); GQA mapping in-kernel
-                ctx = flash_decode_attn(qh.contiguous(), kh, vh, self.scale,
-                                        window=window)
-                context = ctx.permute(0, 2, 1, 3).reshape(
-                    b, 1, self.num_heads_local * self.head_dim)
-                out, _ = self.o_proj(context)
-                out = out + residual if residual is not None else out
-                return (out, present) if use_cache else out
-            chunk = (
+    def _route(self, b, s, sk, dtype, device, has_past=False, use_cache=False,
+               static_cache=False):
+        """The name of the route that serves a call of ``b`` sequences with
+        ``s`` queries on ``sk`` keys (the past length plus ``s``).  Decided
+        from the module's flags, its window and the grad mode before anything
+        is projected; plain values in, so it runs without a GPU.  Packed
+        documents ride on whichever of flash / unfused the shape selects."""
+        if static_cache:
+            return "static_decode"
+        hd = self.head_dim
+        if not has_past:
+            if (
                 self.flash_prefill
-                and past_key_value is not None
-                and s > 1
-                and flash_prefill_available(self.head_dim, q.dtype, q.device, s,
-                                            kh.shape[2])
-            )
-            # a few workgroups on a long cache: flash_prefill="split" sends
-            # the chunk to the split-KV forward where its policy accepts it
-            kv_split = None
-            if chunk and not flash_chunk_pays(b, self.num_heads_local, s,
-                                              kh.shape[2]):
-                chunk = self.flash_prefill == "split" and flash_split_keys(
-                    b, self.num_kv_local, group, s, kh.shape[2]) > 0
-                kv_split = "auto"
-            if chunk:
-                # a chunk behind the cache: query i sits at key pos0 + i.  The
-                # kernel takes the head-major cache through [b, sk, kvh, hd]
-                # views and maps query heads to kv heads itself
-                o = flash_attention(q, kh.permute(0, 2, 1, 3),
-                                    vh.permute(0, 2, 1, 3), self.scale,
-                                    p_drop=0.0, causal=True, training=False,
-                                    window=window, q_offset=pos0,
-                                    kv_split=kv_split)
-                context = o.reshape(b, s, self.num_heads_local * self.head_dim)
-                out, _ = self.o_proj(context)
-                out = out + residual if residual is not None else out
-                return (out, present) if use_cache else out
-            if group > 1:
-                kh = kh.repeat_interleave(group, dim=1)
-                vh = vh.repeat_interleave(group, dim=1)
-            scores = torch.matmul(qh, kh.transpose(-1, -2))
-            causal = past_key_value is None
-            band = None
-            if window is not None:
-                # [b, sq, sk] bool, true = masked: query pos0 + i must not see
-                # key j once (pos0 + i) - j >= W (on top of the causal mask)
-                sk = kh.shape[2]
-                qi = torch.arange(pos0, pos0 + s, device=q.device)[:, None]
-                kj = torch.arange(sk, device=q.device)[None, :]
-                band = ((qi - kj) >= window)[None].expand(b, s, sk)
-            if doc_start is not None:
-                # [b, s, s] bool, true = masked: key j lies before the first
-                # token of query i's document (on top of the causal mask)
-                kj = torch.arange(s, device=q.device)[None, None, :]
-                band = kj < doc_start[:, :, None]
-            probs = fused_scale_mask_softmax(scores, band, scale=self.scale,
-                                             causal=causal,
-                                             training=self.training)
-            ctx = torch.matmul(probs, vh)
-            context = ctx.permute(0, 2, 1, 3).reshape(
-                b, s, self.num_heads_local * self.head_dim
-            )
-            out, _ = self.o_proj(context)
-            out = out + residual if residual is not None else out
-            if use_cache:
-                return out, present
-            return out
+                and use_cache
+                and flash_prefill_available(hd, dtype, device, s, s)
+            ):
+                return "flash_prompt"
+            if (
+                # a windowed model also runs its prompt pass (use_cache) here,
+                # so a long prefill never materializes S x S scores
+                (not use_cache or self.sliding_window is not None)
+                and flash_attention_available(hd, dtype, device, s, s, None)
+            ):
+                return "flash"
+            return "unfused"
+        # what decode_attention_available reads of the query, before it exists
+        query = SimpleNamespace(device=device, dtype=dtype, shape=(s, hd))
+        if attn_ops.decode_attention_available(query, hd):
+            return "decode"
+        chunk = attn_ops.flash_chunk_route(
+            self.flash_prefill, hd, dtype, device, b, self.num_kv_local,
+            self.num_heads_local // self.num_kv_local, s, sk)
+        if chunk is not None:
+            return "flash_chunk_split" if chunk == "split" else "flash_chunk"
+        return "unfused"
 
+    def _output(self, context, present, residual, use_cache):
         out, _ = self.o_proj(context)
-        return out + residual if residual is not None else out
+        out = out + residual if residual is not None else out
+        return (out, present) if use_cache else out
+
+    # -- routes: each calls its op and returns the context, [b, s, nh * hd] ---
+
+    def _static_decode(self, hidden_states, static_cache, position):
+        # hipGraph-capturable decode: RoPE at a device position tensor,
+        # in-place KV insert into [b, kvh, MAX, hd] buffers, fused
+        # flash_decode masked by device int32 kv_len (GQA in-kernel)
+        ck, cv, kv32 = static_cache
+        q, k, v = self._project(hidden_states)
+        # ONE kernel: RoPE(q) -> flash layout, RoPE(k)/copy(v) -> cache
+        # row at the device position (replaces ~15 eager-shaped launches)
+        cos_t, sin_t = _tables(self.max_pos, self.head_dim,
+                               self.rope_theta, hidden_states.device)
+        qo = ext().rope_kv_insert(q, k, v, ck, cv, cos_t, sin_t, position, True)
+        ctx = attn_ops.flash_decode_attn(qo, ck, cv, self.scale, kv_len=kv32,
+                                         window=self.sliding_window)
+        return ctx.permute(0, 2, 1, 3).reshape(ctx.shape[0], 1, -1)
+
+    def _flash(self, q, k, v, doc_bounds, training):
+        # prompt pass of any length (flash_prefill: the key count may be
+        # ragged), training, scoring: no [b, nh, s, s] scores, no
+        # repeat_interleave of K and V
+        o = flash_attention(q, k, v, self.scale, p_drop=0.0, causal=True,
+                            training=training, window=self.sliding_window,
+                            doc_bounds=doc_bounds)
+        return o.reshape(o.shape[0], o.shape[1], -1)
+
+    def _decode(self, qh, kh, vh):
+        # fused single-token decode (K16); GQA mapping in-kernel
+        ctx = attn_ops.flash_decode_attn(qh.contiguous(), kh, vh, self.scale,
+                                         window=self.sliding_window)
+        return ctx.permute(0, 2, 1, 3).reshape(ctx.shape[0], 1, -1)
+
+    def _flash_chunk(self, q, kh, vh, q_offset, kv_split):
+        # a chunk behind the cache: query i sits at key q_offset + i.  The
+        # kernel takes the head-major cache through [b, sk, kvh, hd]
+        # views and maps query heads to kv heads itself
+        o = flash_attention(q, kh.permute(0, 2, 1, 3), vh.permute(0, 2, 1, 3),
+                            self.scale, p_drop=0.0, causal=True, training=False,
+                            window=self.sliding_window, q_offset=q_offset,
+                            kv_split=kv_split)
+        return o.reshape(o.shape[0], o.shape[1], -1)
+
+    def _unfused(self, qh, kh, vh, pos0, doc_start, causal):
+        # unfused path (decode / CPU): [b, nh, s, hs]
+        b, _, s, _ = qh.shape
+        group = self.num_heads_local // self.num_kv_local
+        if group > 1:
+            kh = kh.repeat_interleave(group, dim=1)
+            vh = vh.repeat_interleave(group, dim=1)
+        scores = torch.matmul(qh, kh.transpose(-1, -2))
+        band = None
+        if self.sliding_window is not None:
+            # [b, sq, sk] bool, true = masked: query pos0 + i must not see
+            # key j once (pos0 + i) - j >= W (on top of the causal mask)
+            sk = kh.shape[2]
+            qi = torch.arange(pos0, pos0 + s, device=qh.device)[:, None]
+            kj = torch.arange(sk, device=qh.device)[None, :]
+            band = ((qi - kj) >= self.sliding_window)[None].expand(b, s, sk)
+        if doc_start is not None:
+            # [b, s, s] bool, true = masked: key j lies before the first
+            # token of query i's document (on top of the causal mask)
+            kj = torch.arange(s, device=qh.device)[None, None, :]
+            band = kj < doc_start[:, :, None]
+        probs = fused_scale_mask_softmax(scores, band, scale=self.scale,
+                                         causal=causal, training=self.training)
+        ctx = torch.matmul(probs, vh)
+        return ctx.permute(0, 2, 1, 3).reshape(b, s, -1)
 
 
 def _doc_position_ids(doc_start):

@@ -77,7 +77,7 @@ from ._ext import draw_seed, ext
 __all__ = ["flash_attention", "flash_attention_qkv", "flash_attention_kv",
            "flash_attention_available", "flash_prefill_available",
            "flash_cross_available", "flash_chunk_pays", "flash_split_keys",
-           "mask_kv_len", "bias_alibi_slopes",
+           "flash_chunk_route", "mask_kv_len", "bias_alibi_slopes",
            "bias_rel_table", "window_attention", "window_attention_available"]
 
 
@@ -222,6 +222,26 @@ def flash_split_keys(batch, kv_heads, kv_group, sq, sk):
     in profiles/flash_split_chunk.md): keys per split for a chunk of sq queries
     on sk keys, a multiple of 128, or 0 where splitting does not pay."""
     return ext().flash_split_keys_auto(batch, kv_heads, kv_group, sq, sk)
+
+
+def flash_chunk_route(flash_prefill, head_dim, dtype, device, batch, kv_heads,
+                      kv_group, sq, sk):
+    """Where a multi-token step of sq queries on a cache (sk keys in all) goes
+    under a layer's ``flash_prefill`` setting: ``"flash"`` (the single-pass
+    forward, with ``q_offset = sk - sq``), ``"split"`` (the split-KV forward,
+    ``kv_split="auto"``) or None (the materialized route).  A few workgroups
+    on a long cache do not pay single-pass (``flash_chunk_pays``); only
+    ``flash_prefill="split"`` then asks the split-KV policy."""
+    if not flash_prefill or sq <= 1:
+        return None
+    if not flash_prefill_available(head_dim, dtype, device, sq, sk):
+        return None
+    if flash_chunk_pays(batch, kv_heads * kv_group, sq, sk):
+        return "flash"
+    if flash_prefill == "split" and flash_split_keys(batch, kv_heads, kv_group,
+                                                     sq, sk) > 0:
+        return "split"
+    return None
 
 
 def flash_cross_available(head_dim, dtype, device, sq, sk, pad_mask):

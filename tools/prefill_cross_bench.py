@@ -90,18 +90,16 @@ def llama_pair(kvh, flag=True):
 which = sys.argv[1] if len(sys.argv) > 1 else "all"
 # the chunk tables are what the layers' gate (ops.attention.flash_chunk_pays)
 # was taken from: measure the flash route itself, gated shapes included
-import libai_amd.models.llama as _llama
+import libai_amd.ops.attention as _ops
 
-_gate = _llama.flash_chunk_pays
-_llama.flash_chunk_pays = lambda *a: True
+_gate = _ops.flash_chunk_pays
+_ops.flash_chunk_pays = lambda *a: True
 
 
 def split_mode():
     """Three settings of one layer and its weights, every call through the
     same wrapper: MODE tells the two hooks the layers ask (the gate and the
     policy) what to answer, so no setting pays Python work another does not."""
-    import libai_amd.ops.attention as _ops
-
     policy = _ops.flash_split_keys
     mode = {"n": None}  # "on" | a forced split_keys | None: the layer as shipped
 
@@ -113,8 +111,8 @@ def split_mode():
         n = mode["n"]
         return policy(*a) if n is None else n
 
-    _llama.flash_chunk_pays = gate
-    _llama.flash_split_keys = _ops.flash_split_keys = keys
+    _ops.flash_chunk_pays = gate
+    _ops.flash_split_keys = keys
 
     def call(layer, n, x, past):
         def f():
