@@ -999,6 +999,136 @@ torch::Tensor rope_kv_insert(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   return qo;
 }
 
+// ---------------------------------------------------------------------------
+// FP8 KV cache (kernels/kv_fp8.hip): k8/v8 [B, KVH, MAX, HD] uint8 holding OCP
+// e4m3 bytes, k_scale/v_scale [B, KVH, MAX] fp32, all contiguous.
+// ---------------------------------------------------------------------------
+static void check_fp8_cache(const char* op, const torch::Tensor& ref,
+                            const torch::Tensor& c8, const torch::Tensor& scale,
+                            int64_t B, int64_t KVH, int64_t HD) {
+  TORCH_CHECK(c8.scalar_type() == torch::kUInt8, op,
+              ": the fp8 cache is uint8 storage (view a float8_e4m3fn tensor as "
+              "uint8)");
+  TORCH_CHECK(scale.scalar_type() == torch::kFloat32, op, ": scales must be fp32");
+  TORCH_CHECK(c8.is_cuda() && scale.is_cuda() &&
+                  c8.get_device() == ref.get_device() &&
+                  scale.get_device() == ref.get_device(),
+              op, ": cache and scales must be on the input's device");
+  TORCH_CHECK(c8.dim() == 4 && c8.is_contiguous() && scale.is_contiguous(), op,
+              ": cache [B, KVH, MAX, HD] and scales must be contiguous");
+  TORCH_CHECK(c8.size(0) == B && c8.size(1) == KVH && c8.size(3) == HD, op,
+              ": cache must be [B, KVH, MAX, HD]");
+  TORCH_CHECK(scale.dim() == 3 && scale.size(0) == B && scale.size(1) == KVH &&
+                  scale.size(2) == c8.size(2),
+              op, ": scales must be [B, KVH, MAX]");
+  TORCH_CHECK(HD == 64 || HD == 128, op, ": head dim must be 64 or 128");
+}
+
+// rope_kv_insert onto an fp8 cache: same arguments, the K / V row is quantized
+// with its own scale.  Returns rotated q in [B, NH, 1, HD] bf16.
+torch::Tensor rope_kv_insert_fp8_op(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                                    torch::Tensor k8, torch::Tensor v8,
+                                    torch::Tensor k_scale, torch::Tensor v_scale,
+                                    torch::Tensor cos_t, torch::Tensor sin_t,
+                                    torch::Tensor pos, bool rotate) {
+  TORCH_CHECK(q.dim() == 4 && q.size(1) == 1 && q.stride(3) == 1);
+  TORCH_CHECK(k.dim() == 4 && k.size(1) == 1 && k.stride(3) == 1);
+  TORCH_CHECK(v.dim() == 4 && v.size(1) == 1 && v.stride(3) == 1);
+  TORCH_CHECK(is_bf16(q) && is_bf16(k) && is_bf16(v) && q.is_cuda(),
+              "rope_kv_insert_fp8 takes bf16 cuda q, k, v");
+  TORCH_CHECK(pos.scalar_type() == torch::kInt64 && pos.is_cuda() &&
+              pos.is_contiguous());
+  TORCH_CHECK(pos.numel() == 1 || pos.numel() == q.size(0),
+              "pos must be scalar or per-batch");
+  const int B = (int)q.size(0), NH = (int)q.size(2), HD = (int)q.size(3);
+  const int KVH = (int)k.size(2);
+  TORCH_CHECK(k.size(0) == B && v.size(0) == B && v.size(2) == KVH &&
+              k.size(3) == HD && v.size(3) == HD);
+  check_fp8_cache("rope_kv_insert_fp8", q, k8, k_scale, B, KVH, HD);
+  check_fp8_cache("rope_kv_insert_fp8", q, v8, v_scale, B, KVH, HD);
+  TORCH_CHECK(k8.size(2) == v8.size(2), "k8 and v8 capacities differ");
+  TORCH_CHECK(cos_t.scalar_type() == torch::kFloat32 &&
+              sin_t.scalar_type() == torch::kFloat32 && cos_t.is_cuda() &&
+              sin_t.is_cuda());
+  if (rotate)
+    TORCH_CHECK(cos_t.is_contiguous() && sin_t.is_contiguous() &&
+                    cos_t.dim() == 2 && cos_t.size(1) == HD / 2 &&
+                    cos_t.size(0) >= k8.size(2) && sin_t.sizes() == cos_t.sizes(),
+                "rope tables must be [>= MAX, HD/2] fp32");
+  auto qo = torch::empty({B, NH, 1, HD}, q.options());
+  rope_kv_insert_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(), qo.data_ptr(),
+                     k8.data_ptr(), v8.data_ptr(), k_scale.data_ptr<float>(),
+                     v_scale.data_ptr<float>(), cos_t.data_ptr<float>(),
+                     sin_t.data_ptr<float>(),
+                     (const long long*)pos.data_ptr<int64_t>(), B, NH, KVH, HD,
+                     k8.size(2), q.stride(0), q.stride(2), k.stride(0), k.stride(2),
+                     v.stride(0), v.stride(2), rotate ? 1 : 0,
+                     pos.numel() > 1 ? 1 : 0, cur_stream());
+  check_launch("rope_kv_insert_fp8");
+  return qo;
+}
+
+// src [B, KVH, L, HD] bf16 (any strides with a contiguous last dim, rows
+// 16-byte aligned) -> rows [0, L) of c8 and scale
+void kv_quantize_rows(torch::Tensor src, torch::Tensor c8, torch::Tensor scale) {
+  TORCH_CHECK(src.dim() == 4 && is_bf16(src) && src.is_cuda() && src.stride(3) == 1,
+              "kv_quantize_rows: src must be a bf16 cuda [B, KVH, L, HD] tensor "
+              "with a contiguous last dim");
+  const int64_t B = src.size(0), KVH = src.size(1), L = src.size(2), HD = src.size(3);
+  check_fp8_cache("kv_quantize_rows", src, c8, scale, B, KVH, HD);
+  TORCH_CHECK(L <= c8.size(2), "kv_quantize_rows: L exceeds the cache capacity");
+  TORCH_CHECK(src.stride(0) % 8 == 0 && src.stride(1) % 8 == 0 &&
+                  src.stride(2) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(src.data_ptr()) % 16 == 0,
+              "kv_quantize_rows: src rows must be 16-byte aligned");
+  kv_quantize_rows_bf16(src.data_ptr(), c8.data_ptr(), scale.data_ptr<float>(),
+                        src.stride(0), src.stride(1), src.stride(2), (int)B, (int)KVH,
+                        (int)L, (int)HD, c8.size(2), cur_stream());
+  check_launch("kv_quantize_rows");
+}
+
+// single-query decode attention on the fp8 cache: q [B, H, 1, D] bf16 ->
+// [B, H, 1, D] bf16; all H / KVH <= 8 query heads of a KV head share one pass
+torch::Tensor flash_decode_fp8(torch::Tensor q, torch::Tensor k8, torch::Tensor v8,
+                               torch::Tensor k_scale, torch::Tensor v_scale,
+                               double scale, c10::optional<torch::Tensor> kv_len,
+                               c10::optional<torch::Tensor> alibi_slopes,
+                               int64_t window) {
+  TORCH_CHECK(q.dim() == 4 && q.size(2) == 1, "flash_decode_fp8: q must be [B,H,1,D]");
+  TORCH_CHECK(is_bf16(q) && q.is_cuda() && q.stride(3) == 1,
+              "flash_decode_fp8: q must be a bf16 cuda tensor, last dim contiguous");
+  TORCH_CHECK(!alibi_slopes.has_value(),
+              "flash_decode_fp8 does not take alibi_slopes");
+  TORCH_CHECK(k8.dim() == 4, "flash_decode_fp8: k8 must be [B, KVH, MAX, D]");
+  const int B = (int)q.size(0), H = (int)q.size(1), D = (int)q.size(3);
+  const int KVH = (int)k8.size(1), Skv = (int)k8.size(2);
+  check_fp8_cache("flash_decode_fp8", q, k8, k_scale, B, KVH, D);
+  check_fp8_cache("flash_decode_fp8", q, v8, v_scale, B, KVH, D);
+  TORCH_CHECK(v8.size(2) == Skv, "flash_decode_fp8: k8 and v8 capacities differ");
+  TORCH_CHECK(Skv >= 1, "flash_decode_fp8: empty cache");
+  TORCH_CHECK(KVH >= 1 && H % KVH == 0 && H / KVH <= 8,
+              "flash_decode_fp8 serves 1 <= H / KVH <= 8 query heads per KV head");
+  TORCH_CHECK(q.stride(0) % 8 == 0 && q.stride(1) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "flash_decode_fp8: q rows must be 16-byte aligned");
+  const int* kvl = kv_len_ptr(kv_len, B, /*contiguous=*/true);
+  TORCH_CHECK(window >= 0, "flash_decode_fp8: window must be >= 0 (0 = off)");
+  const int win = (int)std::min<int64_t>(window, Skv);
+  const int S = flash_decode_fp8_num_splits(Skv);
+  auto o = torch::empty({B, H, 1, D}, q.options());
+  auto fopt = q.options().dtype(torch::kFloat32);
+  auto pm = torch::empty({(int64_t)B * H * S}, fopt);
+  auto pl = torch::empty({(int64_t)B * H * S}, fopt);
+  auto pa = torch::empty({(int64_t)B * H * S * D}, fopt);
+  flash_decode_fp8_bf16(q.data_ptr(), k8.data_ptr(), v8.data_ptr(),
+                        k_scale.data_ptr<float>(), v_scale.data_ptr<float>(),
+                        o.data_ptr(), pm.data_ptr<float>(), pl.data_ptr<float>(),
+                        pa.data_ptr<float>(), kvl, q.stride(0), q.stride(1), B, H, KVH,
+                        S, Skv, D, (float)scale, win, cur_stream());
+  check_launch("flash_decode_fp8");
+  return o;
+}
+
 // Single-pass delayed-scaling quantize: bf16 -> fp8 e4m3 with the GIVEN
 // scale; amax of the input accumulates into `amax` (caller derives the
 // next scale).  kernels/quant_fp8.hip.
@@ -1294,6 +1424,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope", &rope, py::arg("x"), py::arg("cos_t"), py::arg("sin_t"),
         py::arg("pos0"), py::arg("bwd"), py::arg("pos_ids") = py::none());
   m.def("rope_kv_insert", &rope_kv_insert);
+  m.def("rope_kv_insert_fp8", &rope_kv_insert_fp8_op);
+  m.def("kv_quantize_rows", &kv_quantize_rows);
+  m.def("flash_decode_fp8", &flash_decode_fp8, py::arg("q"), py::arg("k8"),
+        py::arg("v8"), py::arg("k_scale"), py::arg("v_scale"), py::arg("scale"),
+        py::arg("kv_len"), py::arg("alibi_slopes") = py::none(),
+        py::arg("window") = 0);
   m.def("quant_fp8", &quant_fp8);
   m.def("res_norm_fwd", &res_norm_fwd);
   m.def("swiglu_fwd", &swiglu_fwd);

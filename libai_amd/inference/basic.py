@@ -96,7 +96,7 @@ class TextGenerationPipeline(BasePipeline):
 
     def forward(self, model_inputs, max_length=64, do_sample=False, top_k=0,
                 top_p=1.0, temperature=1.0, num_beams=1, captured=False,
-                **kwargs):
+                kv_cache_dtype="bf16", **kwargs):
         if captured:
             # hipGraph-captured serving loop (GPU, TP=1, greedy or top-k
             # sampling; 2x the eager step — profiles/decode_captured.md)
@@ -113,11 +113,13 @@ class TextGenerationPipeline(BasePipeline):
                 cls = CapturedGPTSampler if is_gpt else CapturedLlamaSampler
                 dec = cls(self.model, max_batch=ids.shape[0],
                           max_seq_len=max_length,
-                          temperature=temperature, top_k=top_k)
+                          temperature=temperature, top_k=top_k,
+                          kv_cache_dtype=kv_cache_dtype)
             else:
                 cls = CapturedGPTDecoder if is_gpt else CapturedLlamaDecoder
                 dec = cls(self.model, max_batch=ids.shape[0],
-                          max_seq_len=max_length)
+                          max_seq_len=max_length,
+                          kv_cache_dtype=kv_cache_dtype)
             new_toks = dec.generate(ids, max_length - ids.shape[1])
             return {"sequences": torch.cat([ids, new_toks], dim=1)}
         gen = Generator(self.model)

@@ -31,6 +31,9 @@ eager; Llama-1B (GQA+RoPE via the fused rope_kv_insert kernel) 3.83 vs
 
 import torch
 
+from ..ops.attention import decode_fp8_available
+from ..ops.kv_cache import alloc_fp8_cache, quantize_rows
+
 __all__ = ["CapturedGPTDecoder", "CapturedLlamaDecoder",
            "SamplingMixin", "CapturedGPTSampler", "CapturedLlamaSampler",
            "ContinuousGPTDecoder", "ContinuousLlamaDecoder",
@@ -46,8 +49,12 @@ class _CapturedDecoderBase:
         tokens = dec.generate(prompt_ids, max_new_tokens=64)  # [b, new]
     """
 
-    def __init__(self, model, max_batch, max_seq_len):
+    def __init__(self, model, max_batch, max_seq_len, kv_cache_dtype="bf16"):
         self.model = model
+        if kv_cache_dtype not in ("bf16", "fp8"):
+            raise ValueError(f'kv_cache_dtype must be "bf16" or "fp8", got '
+                             f"{kv_cache_dtype!r}")
+        self.kv_cache_dtype = kv_cache_dtype
         attn = self._first_attn(model)
         from ..utils import distributed as du
 
@@ -68,14 +75,24 @@ class _CapturedDecoderBase:
         # ONE shared kv_len tensor (all layers decode in lockstep): its
         # advance is a single captured kernel, not one per layer
         self.kv32 = torch.zeros(b, dtype=torch.int32, device=dev)
-        self.caches = [
-            (torch.zeros(b, n_kv, max_seq_len, head_size, device=dev,
-                         dtype=torch.bfloat16),
-             torch.zeros(b, n_kv, max_seq_len, head_size, device=dev,
-                         dtype=torch.bfloat16),
-             self.kv32)
-            for _ in range(self._n_layers(model))
-        ]
+        if kv_cache_dtype == "fp8":
+            # one byte per element plus one fp32 scale per (token, KV head)
+            # row: (k8, v8, k_scale, v_scale, kv32) per layer
+            self._check_fp8(attn, head_size)
+            self.caches = []
+            for _ in range(self._n_layers(model)):
+                k8, ks = alloc_fp8_cache(b, n_kv, max_seq_len, head_size, dev)
+                v8, vs = alloc_fp8_cache(b, n_kv, max_seq_len, head_size, dev)
+                self.caches.append((k8, v8, ks, vs, self.kv32))
+        else:
+            self.caches = [
+                (torch.zeros(b, n_kv, max_seq_len, head_size, device=dev,
+                             dtype=torch.bfloat16),
+                 torch.zeros(b, n_kv, max_seq_len, head_size, device=dev,
+                             dtype=torch.bfloat16),
+                 self.kv32)
+                for _ in range(self._n_layers(model))
+            ]
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
         self.step_idx = torch.zeros(1, dtype=torch.int64, device=dev)
         self.static_tok = torch.zeros(b, 1, dtype=torch.int64, device=dev)
@@ -92,6 +109,25 @@ class _CapturedDecoderBase:
 
     def _n_layers(self, model):
         raise NotImplementedError
+
+    def _check_fp8(self, attn, head_size):
+        """Raise unless the model's static route serves the fp8 cache."""
+        raise NotImplementedError(
+            f"{type(self).__name__} has no fp8 KV cache route")
+
+    def _fill_caches(self, past, L, slot=None):
+        """The prefill copy: rows [0, L) of every layer's cache from
+        ``past_key_values`` (of the whole batch, or of one sequence into
+        ``slot``)."""
+        sel = slice(None) if slot is None else slice(slot, slot + 1)
+        for cache, (pk, pv) in zip(self.caches, past):
+            if self.kv_cache_dtype == "fp8":
+                k8, v8, ks, vs, _ = cache
+                quantize_rows(pk, k8[sel], ks[sel])
+                quantize_rows(pv, v8[sel], vs[sel])
+            else:
+                cache[0][sel, :, :L].copy_(pk)
+                cache[1][sel, :, :L].copy_(pv)
 
     def _logits(self):
         """Run one static step on self.static_tok -> [b, 1, vocab]."""
@@ -132,9 +168,7 @@ class _CapturedDecoderBase:
         out = self.model(input_ids=prompt_ids.to(self.device), use_cache=True)
         past = out["past_key_values"]
         logits = out["prediction_scores"]
-        for (ck, cv, _), (pk, pv) in zip(self.caches, past):
-            ck[:, :, :L].copy_(pk)
-            cv[:, :, :L].copy_(pv)
+        self._fill_caches(past, L)
         first = self._select(logits[:, -1, :])  # token at pos L
 
         if self.out_tokens is None or self.out_tokens.shape[1] < max_new_tokens:
@@ -201,6 +235,14 @@ class CapturedLlamaDecoder(_CapturedDecoderBase):
     def _n_layers(self, model):
         return len(model.model.layers)
 
+    def _check_fp8(self, attn, head_size):
+        group = attn.num_heads_local // attn.num_kv_local
+        if not decode_fp8_available(head_size, group):
+            raise RuntimeError(
+                f"the fp8 KV cache serves head size 64 or 128 and at most 8 "
+                f"query heads per KV head, got head size {head_size}, group "
+                f"{group}")
+
     def _logits(self):
         return self.model(self.static_tok, static_caches=self.caches,
                           position=self.pos)
@@ -231,16 +273,18 @@ class SamplingMixin:
 
 class CapturedGPTSampler(SamplingMixin, CapturedGPTDecoder):
     def __init__(self, model, max_batch, max_seq_len, temperature=1.0,
-                 top_k=0):
-        super().__init__(model, max_batch, max_seq_len)
+                 top_k=0, kv_cache_dtype="bf16"):
+        super().__init__(model, max_batch, max_seq_len,
+                         kv_cache_dtype=kv_cache_dtype)
         self.temperature = temperature
         self.top_k = top_k
 
 
 class CapturedLlamaSampler(SamplingMixin, CapturedLlamaDecoder):
     def __init__(self, model, max_batch, max_seq_len, temperature=1.0,
-                 top_k=0):
-        super().__init__(model, max_batch, max_seq_len)
+                 top_k=0, kv_cache_dtype="bf16"):
+        super().__init__(model, max_batch, max_seq_len,
+                         kv_cache_dtype=kv_cache_dtype)
         self.temperature = temperature
         self.top_k = top_k
 
@@ -323,9 +367,7 @@ class _ContinuousMixin:
         L = prompt_ids.shape[1]
         assert L + 1 < self.max_seq_len
         out = self.model(input_ids=prompt_ids, use_cache=True)
-        for (ck, cv, _), (pk, pv) in zip(self.caches, out["past_key_values"]):
-            ck[slot, :, :L].copy_(pk[0])
-            cv[slot, :, :L].copy_(pv[0])
+        self._fill_caches(out["past_key_values"], L, slot=slot)
         first = self._select(out["prediction_scores"][:, -1, :])
         self.ring[slot, 0] = first[0, 0]
         self.static_tok[slot, 0] = first[0, 0]
@@ -397,15 +439,19 @@ class _ContinuousMixin:
 
 
 class ContinuousGPTDecoder(_ContinuousMixin, CapturedGPTDecoder):
-    def __init__(self, model, max_batch, max_seq_len, ring_cap=64):
-        super().__init__(model, max_batch, max_seq_len)
+    def __init__(self, model, max_batch, max_seq_len, ring_cap=64,
+                 kv_cache_dtype="bf16"):
+        super().__init__(model, max_batch, max_seq_len,
+                         kv_cache_dtype=kv_cache_dtype)
         self.ring_cap = ring_cap
         self._init_cont()
 
 
 class ContinuousLlamaDecoder(_ContinuousMixin, CapturedLlamaDecoder):
-    def __init__(self, model, max_batch, max_seq_len, ring_cap=64):
-        super().__init__(model, max_batch, max_seq_len)
+    def __init__(self, model, max_batch, max_seq_len, ring_cap=64,
+                 kv_cache_dtype="bf16"):
+        super().__init__(model, max_batch, max_seq_len,
+                         kv_cache_dtype=kv_cache_dtype)
         self.ring_cap = ring_cap
         self._init_cont()
 
@@ -413,15 +459,17 @@ class ContinuousLlamaDecoder(_ContinuousMixin, CapturedLlamaDecoder):
 class ContinuousGPTSampler(SamplingMixin, ContinuousGPTDecoder):
     # continuous batching with in-graph top-k/temperature sampling
     def __init__(self, model, max_batch, max_seq_len, ring_cap=64,
-                 temperature=1.0, top_k=0):
-        super().__init__(model, max_batch, max_seq_len, ring_cap=ring_cap)
+                 temperature=1.0, top_k=0, kv_cache_dtype="bf16"):
+        super().__init__(model, max_batch, max_seq_len, ring_cap=ring_cap,
+                         kv_cache_dtype=kv_cache_dtype)
         self.temperature = temperature
         self.top_k = top_k
 
 
 class ContinuousLlamaSampler(SamplingMixin, ContinuousLlamaDecoder):
     def __init__(self, model, max_batch, max_seq_len, ring_cap=64,
-                 temperature=1.0, top_k=0):
-        super().__init__(model, max_batch, max_seq_len, ring_cap=ring_cap)
+                 temperature=1.0, top_k=0, kv_cache_dtype="bf16"):
+        super().__init__(model, max_batch, max_seq_len, ring_cap=ring_cap,
+                         kv_cache_dtype=kv_cache_dtype)
         self.temperature = temperature
         self.top_k = top_k

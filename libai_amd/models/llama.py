@@ -229,15 +229,29 @@ class LlamaAttention(nn.Module):
         # hipGraph-capturable decode: RoPE at a device position tensor,
         # in-place KV insert into [b, kvh, MAX, hd] buffers, fused
         # flash_decode masked by device int32 kv_len (GQA in-kernel)
-        ck, cv, kv32 = static_cache
+        # A static cache of five with one-byte data, (k8, v8, k_scale, v_scale,
+        # kv32), is the e4m3 cache (ops/kv_cache.py): same two steps on the
+        # quantizing insert and the packed-GQA decode kernel.
         q, k, v = self._project(hidden_states)
         # ONE kernel: RoPE(q) -> flash layout, RoPE(k)/copy(v) -> cache
         # row at the device position (replaces ~15 eager-shaped launches)
         cos_t, sin_t = _tables(self.max_pos, self.head_dim,
                                self.rope_theta, hidden_states.device)
-        qo = ext().rope_kv_insert(q, k, v, ck, cv, cos_t, sin_t, position, True)
-        ctx = attn_ops.flash_decode_attn(qo, ck, cv, self.scale, kv_len=kv32,
-                                         window=self.sliding_window)
+        if len(static_cache) == 5:
+            k8, v8, k_scale, v_scale, kv32 = static_cache
+            if k8.dtype != torch.uint8:
+                raise TypeError("a five-entry static cache is the fp8 cache: "
+                                f"uint8 data, got {k8.dtype}")
+            qo = ext().rope_kv_insert_fp8(q, k, v, k8, v8, k_scale, v_scale,
+                                          cos_t, sin_t, position, True)
+            ctx = attn_ops.flash_decode_attn_fp8(
+                qo, k8, v8, k_scale, v_scale, self.scale, kv_len=kv32,
+                window=self.sliding_window)
+        else:
+            ck, cv, kv32 = static_cache
+            qo = ext().rope_kv_insert(q, k, v, ck, cv, cos_t, sin_t, position, True)
+            ctx = attn_ops.flash_decode_attn(qo, ck, cv, self.scale, kv_len=kv32,
+                                             window=self.sliding_window)
         return ctx.permute(0, 2, 1, 3).reshape(ctx.shape[0], 1, -1)
 
     def _flash(self, q, k, v, doc_bounds, training):

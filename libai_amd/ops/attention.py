@@ -484,6 +484,54 @@ def flash_decode_attn(q, k, v, scale, kv_len=None, alibi_slopes=None,
                               variant.window)
 
 
+FP8_DECODE_MAX_GROUP = 8
+
+
+def decode_fp8_available(head_dim, group):
+    """Whether ``flash_decode_attn_fp8`` serves heads of ``head_dim`` with
+    ``group`` query heads per KV head."""
+    return head_dim in (64, 128) and 1 <= group <= FP8_DECODE_MAX_GROUP
+
+
+def flash_decode_attn_fp8(q, k8, v8, k_scale, v_scale, scale, kv_len=None,
+                          window=None, alibi_slopes=None):
+    """q [B, H, 1, D] bf16 on the e4m3 KV cache (ops/kv_cache.py): k8/v8
+    [B, KVH, MAX, D] one byte per element (uint8, or float8_e4m3fn which is
+    viewed as uint8), k_scale/v_scale [B, KVH, MAX] fp32 -> [B, H, 1, D] bf16.
+
+    One pass over a KV head's keys serves all H / KVH <= 8 of its query heads
+    (scores and PV on the matrix pipe, kernels/kv_fp8.hip).  kv_len: optional
+    int32 [B]; window: optional int W, the keys [max(0, kv_len[b] - W),
+    kv_len[b]).  There is no ALiBi form: ``alibi_slopes`` must stay None."""
+    if alibi_slopes is not None:
+        raise ValueError("flash_decode_attn_fp8 does not accept alibi_slopes")
+    if q.dim() != 4 or q.shape[2] != 1:
+        raise ValueError(f"q must be [B, H, 1, D], got {tuple(q.shape)}")
+    if k8.dim() != 4 or tuple(v8.shape) != tuple(k8.shape):
+        raise ValueError("k8 and v8 must be [B, KVH, MAX, D] of one shape, got "
+                         f"{tuple(k8.shape)} and {tuple(v8.shape)}")
+    b, h, _, d = q.shape
+    kvh = k8.shape[1]
+    if k8.shape[0] != b or k8.shape[3] != d or kvh < 1 or h % kvh != 0:
+        raise ValueError(f"cache {tuple(k8.shape)} does not fit q {tuple(q.shape)}")
+    if not decode_fp8_available(d, h // kvh):
+        raise ValueError(
+            f"flash_decode_attn_fp8 serves head size 64 or 128 and at most "
+            f"{FP8_DECODE_MAX_GROUP} query heads per KV head, got head size {d}, "
+            f"group {h // kvh}")
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if tuple(s.shape) != tuple(k8.shape[:3]) or s.dtype != torch.float32:
+            raise ValueError(f"{name} must be fp32 [B, KVH, MAX] = "
+                             f"{tuple(k8.shape[:3])}, got {s.dtype} {tuple(s.shape)}")
+    window = 0 if window is None else int(window)
+    if window < 0:
+        raise ValueError(f"window must be >= 1 (or None/0 for off), got {window}")
+    k8, v8 = (t.view(torch.uint8) if t.dtype == torch.float8_e4m3fn else t
+              for t in (k8, v8))
+    return ext().flash_decode_fp8(q, k8, v8, k_scale, v_scale, scale, kv_len, None,
+                                  window)
+
+
 # ---------------------------------------------------------------------------
 # window attention (Swin)
 # ---------------------------------------------------------------------------
