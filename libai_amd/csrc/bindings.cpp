@@ -1025,15 +1025,18 @@ static void check_fp8_cache(const char* op, const torch::Tensor& ref,
 }
 
 // rope_kv_insert onto an fp8 cache: same arguments, the K / V row is quantized
-// with its own scale.  Returns rotated q in [B, NH, 1, HD] bf16.
+// with its own scale.  q, k, v are [B, T, heads, HD], 1 <= T <= 32: token t goes
+// to position pos[b] + t.  Returns rotated q in [B, NH, T, HD] bf16.
 torch::Tensor rope_kv_insert_fp8_op(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                     torch::Tensor k8, torch::Tensor v8,
                                     torch::Tensor k_scale, torch::Tensor v_scale,
                                     torch::Tensor cos_t, torch::Tensor sin_t,
                                     torch::Tensor pos, bool rotate) {
-  TORCH_CHECK(q.dim() == 4 && q.size(1) == 1 && q.stride(3) == 1);
-  TORCH_CHECK(k.dim() == 4 && k.size(1) == 1 && k.stride(3) == 1);
-  TORCH_CHECK(v.dim() == 4 && v.size(1) == 1 && v.stride(3) == 1);
+  TORCH_CHECK(q.dim() == 4 && q.size(1) >= 1 && q.size(1) <= 32 && q.stride(3) == 1,
+              "rope_kv_insert_fp8: q must be [B, T, NH, HD], 1 <= T <= 32");
+  const int T = (int)q.size(1);
+  TORCH_CHECK(k.dim() == 4 && k.size(1) == T && k.stride(3) == 1);
+  TORCH_CHECK(v.dim() == 4 && v.size(1) == T && v.stride(3) == 1);
   TORCH_CHECK(is_bf16(q) && is_bf16(k) && is_bf16(v) && q.is_cuda(),
               "rope_kv_insert_fp8 takes bf16 cuda q, k, v");
   TORCH_CHECK(pos.scalar_type() == torch::kInt64 && pos.is_cuda() &&
@@ -1055,15 +1058,15 @@ torch::Tensor rope_kv_insert_fp8_op(torch::Tensor q, torch::Tensor k, torch::Ten
                     cos_t.dim() == 2 && cos_t.size(1) == HD / 2 &&
                     cos_t.size(0) >= k8.size(2) && sin_t.sizes() == cos_t.sizes(),
                 "rope tables must be [>= MAX, HD/2] fp32");
-  auto qo = torch::empty({B, NH, 1, HD}, q.options());
+  auto qo = torch::empty({B, NH, T, HD}, q.options());
   rope_kv_insert_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(), qo.data_ptr(),
                      k8.data_ptr(), v8.data_ptr(), k_scale.data_ptr<float>(),
                      v_scale.data_ptr<float>(), cos_t.data_ptr<float>(),
                      sin_t.data_ptr<float>(),
-                     (const long long*)pos.data_ptr<int64_t>(), B, NH, KVH, HD,
-                     k8.size(2), q.stride(0), q.stride(2), k.stride(0), k.stride(2),
-                     v.stride(0), v.stride(2), rotate ? 1 : 0,
-                     pos.numel() > 1 ? 1 : 0, cur_stream());
+                     (const long long*)pos.data_ptr<int64_t>(), B, T, NH, KVH, HD,
+                     k8.size(2), q.stride(0), q.stride(1), q.stride(2), k.stride(0),
+                     k.stride(1), k.stride(2), v.stride(0), v.stride(1), v.stride(2),
+                     rotate ? 1 : 0, pos.numel() > 1 ? 1 : 0, cur_stream());
   check_launch("rope_kv_insert_fp8");
   return qo;
 }
@@ -1126,6 +1129,50 @@ torch::Tensor flash_decode_fp8(torch::Tensor q, torch::Tensor k8, torch::Tensor 
                         pa.data_ptr<float>(), kvl, q.stride(0), q.stride(1), B, H, KVH,
                         S, Skv, D, (float)scale, win, cur_stream());
   check_launch("flash_decode_fp8");
+  return o;
+}
+
+// a step of T tokens on the fp8 cache: q [B, H, T, D] bf16 -> [B, H, T, D] bf16,
+// token t at position kv_len[b] - T + t (kv_len: the length after the step's
+// insert), causal and windowed per token; T * (H / KVH) columns share one pass
+torch::Tensor flash_chunk_fp8(torch::Tensor q, torch::Tensor k8, torch::Tensor v8,
+                              torch::Tensor k_scale, torch::Tensor v_scale,
+                              double scale, c10::optional<torch::Tensor> kv_len,
+                              int64_t window) {
+  TORCH_CHECK(q.dim() == 4 && q.size(2) >= 1 && q.size(2) <= 32,
+              "flash_chunk_fp8: q must be [B,H,T,D], 1 <= T <= 32");
+  TORCH_CHECK(is_bf16(q) && q.is_cuda() && q.stride(3) == 1,
+              "flash_chunk_fp8: q must be a bf16 cuda tensor, last dim contiguous");
+  TORCH_CHECK(k8.dim() == 4, "flash_chunk_fp8: k8 must be [B, KVH, MAX, D]");
+  const int B = (int)q.size(0), H = (int)q.size(1), T = (int)q.size(2);
+  const int D = (int)q.size(3);
+  const int KVH = (int)k8.size(1), Skv = (int)k8.size(2);
+  check_fp8_cache("flash_chunk_fp8", q, k8, k_scale, B, KVH, D);
+  check_fp8_cache("flash_chunk_fp8", q, v8, v_scale, B, KVH, D);
+  TORCH_CHECK(v8.size(2) == Skv, "flash_chunk_fp8: k8 and v8 capacities differ");
+  TORCH_CHECK(Skv >= 1, "flash_chunk_fp8: empty cache");
+  TORCH_CHECK(KVH >= 1 && H % KVH == 0 && H / KVH <= 8,
+              "flash_chunk_fp8 serves 1 <= H / KVH <= 8 query heads per KV head");
+  TORCH_CHECK(q.stride(0) % 8 == 0 && q.stride(1) % 8 == 0 && q.stride(2) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "flash_chunk_fp8: q rows must be 16-byte aligned");
+  const int* kvl = kv_len_ptr(kv_len, B, /*contiguous=*/true);
+  TORCH_CHECK(window >= 0, "flash_chunk_fp8: window must be >= 0 (0 = off)");
+  const int win = (int)std::min<int64_t>(window, Skv);
+  const int S = flash_decode_fp8_num_splits(Skv);
+  auto o = torch::empty({B, H, T, D}, q.options());
+  auto fopt = q.options().dtype(torch::kFloat32);
+  const int64_t rows = (int64_t)B * H * T * S;
+  auto pm = torch::empty({rows}, fopt);
+  auto pl = torch::empty({rows}, fopt);
+  auto pa = torch::empty({rows * D}, fopt);
+  flash_chunk_fp8_bf16(q.data_ptr(), k8.data_ptr(), v8.data_ptr(),
+                       k_scale.data_ptr<float>(), v_scale.data_ptr<float>(),
+                       o.data_ptr(), pm.data_ptr<float>(), pl.data_ptr<float>(),
+                       pa.data_ptr<float>(), kvl, q.stride(0), q.stride(1),
+                       q.stride(2), B, H, KVH, T, S, Skv, D, (float)scale, win,
+                       cur_stream());
+  check_launch("flash_chunk_fp8");
   return o;
 }
 
@@ -1430,6 +1477,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v8"), py::arg("k_scale"), py::arg("v_scale"), py::arg("scale"),
         py::arg("kv_len"), py::arg("alibi_slopes") = py::none(),
         py::arg("window") = 0);
+  m.def("flash_chunk_fp8", &flash_chunk_fp8, py::arg("q"), py::arg("k8"),
+        py::arg("v8"), py::arg("k_scale"), py::arg("v_scale"), py::arg("scale"),
+        py::arg("kv_len") = py::none(), py::arg("window") = 0);
   m.def("quant_fp8", &quant_fp8);
   m.def("res_norm_fwd", &res_norm_fwd);
   m.def("swiglu_fwd", &swiglu_fwd);

@@ -115,13 +115,24 @@ void flash_decode_split_bf16(const void* q, const void* k, const void* v, void* 
 // rope_kv_insert_bf16; kv_quantize_rows takes a [B, KVH, L, HD] bf16 source by
 // element strides; the decode takes q/o [B, H, 1, D] (o contiguous) and
 // part_m/part_l [B, H, S], part_acc [B, H, S, D], S = flash_decode_fp8_num_splits.
+// A step of T tokens: the insert takes q, k, v [B, T, heads, HD] by (batch,
+// token, head) strides and writes qo [B, NH, T, HD]; flash_chunk_fp8 takes q
+// [B, H, T, D] by (batch, head, token) strides, o [B, H, T, D] contiguous and
+// partials with a token axis, [B, H, T, S] and [B, H, T, S, D].
 void rope_kv_insert_fp8(const void* q, const void* k, const void* v, void* qo,
                         void* k8, void* v8, float* k_scale, float* v_scale,
                         const float* cos_t, const float* sin_t,
-                        const long long* pos_p, int B, int NH, int KVH, int HD,
-                        int64_t max_len, int64_t q_sb, int64_t q_sh, int64_t k_sb,
-                        int64_t k_sh, int64_t v_sb, int64_t v_sh, int rotate,
+                        const long long* pos_p, int B, int T, int NH, int KVH,
+                        int HD, int64_t max_len, int64_t q_sb, int64_t q_st,
+                        int64_t q_sh, int64_t k_sb, int64_t k_st, int64_t k_sh,
+                        int64_t v_sb, int64_t v_st, int64_t v_sh, int rotate,
                         int per_batch_pos, hipStream_t stream);
+void flash_chunk_fp8_bf16(const void* q, const void* k8, const void* v8,
+                          const float* k_scale, const float* v_scale, void* o,
+                          float* part_m, float* part_l, float* part_acc,
+                          const int* kv_len, int64_t q_sb, int64_t q_sh,
+                          int64_t q_st, int B, int H, int KVH, int T, int S, int Skv,
+                          int D, float scale, int window, hipStream_t stream);
 void kv_quantize_rows_bf16(const void* src, void* dst, float* scale, int64_t s_sb,
                            int64_t s_sh, int64_t s_sl, int B, int KVH, int L, int HD,
                            int64_t max_len, hipStream_t stream);

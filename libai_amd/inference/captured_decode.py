@@ -32,7 +32,7 @@ eager; Llama-1B (GQA+RoPE via the fused rope_kv_insert kernel) 3.83 vs
 import torch
 
 from ..ops.attention import decode_fp8_available
-from ..ops.kv_cache import alloc_fp8_cache, quantize_rows
+from ..ops.kv_cache import accept_greedy, alloc_fp8_cache, quantize_rows
 
 __all__ = ["CapturedGPTDecoder", "CapturedLlamaDecoder",
            "SamplingMixin", "CapturedGPTSampler", "CapturedLlamaSampler",
@@ -243,9 +243,10 @@ class CapturedLlamaDecoder(_CapturedDecoderBase):
                 f"query heads per KV head, got head size {head_size}, group "
                 f"{group}")
 
-    def _logits(self):
-        return self.model(self.static_tok, static_caches=self.caches,
-                          position=self.pos)
+    def _logits(self, tokens=None):
+        # tokens [b, T]: a multi-token step from self.pos (the fp8 cache only)
+        return self.model(self.static_tok if tokens is None else tokens,
+                          static_caches=self.caches, position=self.pos)
 
 
 class SamplingMixin:
@@ -303,6 +304,7 @@ class _ContinuousMixin:
         dec.step(16)                           # 16 graph replays
         dec.add_request(1, prompt_b)           # admit mid-flight
         dec.step(16)
+        n = dec.speculate(draft)               # fp8 cache: verify K draft tokens
         toks_a = dec.tokens(0)                 # generated tokens so far
         dec.release(0)                         # free the slot
 
@@ -388,6 +390,50 @@ class _ContinuousMixin:
             self._capture()
         for _ in range(n):
             self.graph.replay()
+
+    def _speculate_logits(self, draft):
+        """Feed ``[static_tok, draft]`` at the per-slot positions as ONE step of
+        K + 1 tokens -> logits [b, K + 1, vocab].  Leaves kv32 at pos + K + 1."""
+        if isinstance(self, SamplingMixin):
+            raise NotImplementedError("speculate verifies greedy selection only")
+        if self.kv_cache_dtype != "fp8":
+            raise NotImplementedError("speculate needs kv_cache_dtype=\"fp8\": "
+                                      "the bf16 cache has no multi-token step")
+        if (draft.dim() != 2 or draft.shape[0] != self.max_batch
+                or not 1 <= draft.shape[1] <= 31 or draft.dtype != torch.int64):
+            raise ValueError(f"draft must be int64 [max_batch, K], 1 <= K <= 31, "
+                             f"got {draft.dtype} {tuple(draft.shape)}")
+        toks = torch.cat([self.static_tok, draft.to(self.device)], dim=1)
+        self.kv32.copy_(self.pos + toks.shape[1])  # length after all inserts
+        return self._logits(toks)
+
+    @torch.no_grad()
+    def speculate(self, draft):
+        """Verify a greedy draft: ``draft`` int64 [max_batch, K], 1 <= K <= 31,
+        the K tokens proposed to follow each slot's current token.  One eager
+        step of K + 1 tokens scores them all; slot b keeps its n[b] leading
+        draft tokens that the model would have picked itself plus the model's
+        own next token, so it gains n[b] + 1 tokens of the plain greedy stream.
+        Returns n [max_batch] (on the device; nothing here reads it back).
+
+        Rejected rows stay in the cache above kv_len: never read, overwritten
+        by later steps.  The caller keeps pos + K + 1 <= max_seq_len.  fp8 cache
+        and greedy selection only."""
+        logits = self._speculate_logits(draft)
+        k1 = logits.shape[1]
+        target = logits.argmax(dim=-1)  # [b, K + 1]
+        n, nxt = accept_greedy(draft.to(self.device), target)
+        # ring[slot_step + i] = target[:, i] for i <= n; the rest keep theirs
+        idx = (self.slot_step + torch.arange(k1, device=self.device)
+               ).remainder(self.ring_cap)
+        keep = torch.arange(k1, device=self.device)[None, :] <= n[:, None]
+        self.ring.scatter_(1, idx, torch.where(keep, target,
+                                               self.ring.gather(1, idx)))
+        self.static_tok.copy_(nxt)
+        self.pos.add_(n + 1)
+        self.kv32.copy_(self.pos + 1)
+        self.slot_step.add_((n + 1)[:, None])
+        return n
 
     def tokens(self, slot):
         """Generated tokens for ``slot`` so far (host sync; ring must not

@@ -232,6 +232,12 @@ class LlamaAttention(nn.Module):
         # A static cache of five with one-byte data, (k8, v8, k_scale, v_scale,
         # kv32), is the e4m3 cache (ops/kv_cache.py): same two steps on the
         # quantizing insert and the packed-GQA decode kernel.
+        # A step of T tokens (hidden_states [b, T, h], the fp8 cache only):
+        # `position` is the first token's, kv32 the length after all T inserts.
+        steps = hidden_states.shape[1]
+        if steps > 1 and len(static_cache) != 5:
+            raise NotImplementedError("a multi-token static step needs the fp8 "
+                                      "KV cache")
         q, k, v = self._project(hidden_states)
         # ONE kernel: RoPE(q) -> flash layout, RoPE(k)/copy(v) -> cache
         # row at the device position (replaces ~15 eager-shaped launches)
@@ -252,7 +258,7 @@ class LlamaAttention(nn.Module):
             qo = ext().rope_kv_insert(q, k, v, ck, cv, cos_t, sin_t, position, True)
             ctx = attn_ops.flash_decode_attn(qo, ck, cv, self.scale, kv_len=kv32,
                                              window=self.sliding_window)
-        return ctx.permute(0, 2, 1, 3).reshape(ctx.shape[0], 1, -1)
+        return ctx.permute(0, 2, 1, 3).reshape(ctx.shape[0], steps, -1)
 
     def _flash(self, q, k, v, doc_bounds, training):
         # prompt pass of any length (flash_prefill: the key count may be

@@ -485,6 +485,7 @@ def flash_decode_attn(q, k, v, scale, kv_len=None, alibi_slopes=None,
 
 
 FP8_DECODE_MAX_GROUP = 8
+FP8_DECODE_MAX_TOKENS = 32  # tokens per sequence in one multi-token step
 
 
 def decode_fp8_available(head_dim, group):
@@ -495,18 +496,26 @@ def decode_fp8_available(head_dim, group):
 
 def flash_decode_attn_fp8(q, k8, v8, k_scale, v_scale, scale, kv_len=None,
                           window=None, alibi_slopes=None):
-    """q [B, H, 1, D] bf16 on the e4m3 KV cache (ops/kv_cache.py): k8/v8
-    [B, KVH, MAX, D] one byte per element (uint8, or float8_e4m3fn which is
-    viewed as uint8), k_scale/v_scale [B, KVH, MAX] fp32 -> [B, H, 1, D] bf16.
+    """q [B, H, T, D] bf16, 1 <= T <= 32, on the e4m3 KV cache
+    (ops/kv_cache.py): k8/v8 [B, KVH, MAX, D] one byte per element (uint8, or
+    float8_e4m3fn which is viewed as uint8), k_scale/v_scale [B, KVH, MAX] fp32
+    -> [B, H, T, D] bf16.
 
     One pass over a KV head's keys serves all H / KVH <= 8 of its query heads
     (scores and PV on the matrix pipe, kernels/kv_fp8.hip).  kv_len: optional
     int32 [B]; window: optional int W, the keys [max(0, kv_len[b] - W),
-    kv_len[b]).  There is no ALiBi form: ``alibi_slopes`` must stay None."""
+    kv_len[b]).  There is no ALiBi form: ``alibi_slopes`` must stay None.
+
+    T > 1 is a multi-token step (a speculative draft to verify, a re-fed
+    suffix): kv_len is the length after the step's insert, token t sits at
+    position p = kv_len[b] - T + t and sees the keys j <= p (with a window,
+    p - j < W); rows with p < 0 are zeros.  The tokens share the pass over the
+    keys, and token t carries the bits of a T = 1 call at kv_len - (T - 1 - t)."""
     if alibi_slopes is not None:
         raise ValueError("flash_decode_attn_fp8 does not accept alibi_slopes")
-    if q.dim() != 4 or q.shape[2] != 1:
-        raise ValueError(f"q must be [B, H, 1, D], got {tuple(q.shape)}")
+    if q.dim() != 4 or not 1 <= q.shape[2] <= FP8_DECODE_MAX_TOKENS:
+        raise ValueError(f"q must be [B, H, T, D] with 1 <= T <= "
+                         f"{FP8_DECODE_MAX_TOKENS}, got {tuple(q.shape)}")
     if k8.dim() != 4 or tuple(v8.shape) != tuple(k8.shape):
         raise ValueError("k8 and v8 must be [B, KVH, MAX, D] of one shape, got "
                          f"{tuple(k8.shape)} and {tuple(v8.shape)}")
@@ -528,8 +537,10 @@ def flash_decode_attn_fp8(q, k8, v8, k_scale, v_scale, scale, kv_len=None,
         raise ValueError(f"window must be >= 1 (or None/0 for off), got {window}")
     k8, v8 = (t.view(torch.uint8) if t.dtype == torch.float8_e4m3fn else t
               for t in (k8, v8))
-    return ext().flash_decode_fp8(q, k8, v8, k_scale, v_scale, scale, kv_len, None,
-                                  window)
+    if q.shape[2] == 1:
+        return ext().flash_decode_fp8(q, k8, v8, k_scale, v_scale, scale, kv_len,
+                                      None, window)
+    return ext().flash_chunk_fp8(q, k8, v8, k_scale, v_scale, scale, kv_len, window)
 
 
 # ---------------------------------------------------------------------------

@@ -45,6 +45,21 @@ def quantize_rows(src, c8, scale):
     ext().kv_quantize_rows(src, c8, scale)
 
 
+def accept_greedy(draft, target):
+    """Greedy speculative acceptance, on the device with no host read.
+
+    ``draft`` [B, K] are the proposed tokens, ``target`` [B, K + 1] the model's
+    argmax after the last accepted token and after each draft token.  ->
+    ``(n [B], next_tok [B, 1])``: n is the length of the leading run with
+    ``draft[:, i] == target[:, i]``, next_tok the model's own token behind it,
+    ``target[b, n[b]]``."""
+    if draft.dim() != 2 or tuple(target.shape) != (draft.shape[0], draft.shape[1] + 1):
+        raise ValueError(f"draft [B, K] and target [B, K + 1], got "
+                         f"{tuple(draft.shape)} and {tuple(target.shape)}")
+    n = (draft == target[:, :-1]).long().cumprod(dim=1).sum(dim=1)
+    return n, target.gather(1, n[:, None])
+
+
 def dequantize(c8, scale):
     """fp32 values of a cache half, plain torch (tests and debugging)."""
     return c8.view(torch.float8_e4m3fn).to(torch.float32) * scale.unsqueeze(-1)
